@@ -4,15 +4,26 @@
 Workload (BASELINE.json configs[1], SURVEY.md 8d "cfg2"): IBA + DORT, 20 layers, 32 streams, 5 AMSR-E channels
 (10.65/18.7/23.8/36.5/89 GHz, 55 deg, V+H), batch of 1024 synthetic snowpacks per GPU = 5120 solves per step.
 A step = one pass of the hot path over that batch with the inputs already resident in HBM (packed and uploaded once,
-before timing); `value` is that rate.  The same JSON line also carries, measured in the same run:
+before timing); `value` is that rate, `ms_per_step` the time of one timed step.  The line also carries `roofline`: 68 sum
+N_l^3 flops / summed HIP-event time of the pipeline kernels of the timed steps, against the FP64 peak.
+
+A plain run does only that: set up, warm up, time --steps steps, print the line.  With `--full` the same JSON line also
+carries, measured in the same run after the timed steps:
 
 * `pcie_inclusive`  -- the one-shot C entry point smrt_dort_run on host buffers: H2D of the packed inputs, the kernels,
                        D2H of results and diagnostics (SURVEY.md 8d counts the metric this way);
 * `model_run`       -- Model.run -> HipBatchRunner -> Result on 1024 Snowpack objects: the plugin surface end to end;
-* `roofline`        -- 68 sum N_l^3 flops / summed HIP-event time of the pipeline kernels, against the FP64 peak;
-* `cpu_baseline`    -- the CPU oracle on this box's cores, one BLAS thread per worker (N = 1 only).
+* `roofline.per_kernel` -- HIP-event time per kernel kind from three instrumented launches;
+* `roofline.traffic` / `hbm` -- HBM bytes per launch from the committed PMC summary (profiles/hbm_traffic.json);
+* `cpu_baseline`    -- the CPU oracle on this box's cores, one BLAS thread per worker (N = 1 only);
+* `other_configs`   -- short runs of the configs[2] and configs[3] shapes.
+
+`--dump-outputs DIR` writes what the last timed step computed, as a caller of the timed path receives it (brightness
+temperatures / intensities, status and the per-pair diagnostics), to DIR/<name>.npy in float64; the inputs are seeded, so
+two builds can be compared output for output.
 
     python bench.py --gpus 1 --steps 20 --warmup 3
+    python bench.py --gpus 1 --steps 20 --warmup 3 --full
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \\
         bench.py --gpus N --steps K --warmup W
 
@@ -26,7 +37,7 @@ Prints ONE JSON line on rank 0.
 
 `--config 2 | 3` runs the same measurement on the shapes of BASELINE configs[2] (DMRT-QCA-SR, 50 layers, 64 streams,
 7 AMSR2 frequencies) and configs[3] (IBA active, Sentinel-1, 30 layers, 128 streams, m_max 2) with `--snowpacks S` per
-GPU; the CPU baseline and the secondary measurements belong to the default configuration only.
+GPU; the CPU baseline and the secondary measurements (`--full`) belong to the default configuration only.
 """
 import os
 
@@ -294,6 +305,25 @@ def other_config(config, n_snowpacks, steps, local_rank):
         ctx.close()
 
 
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(directory, arrays):
+    """arrays: {name: array with one row per pair}, written as DIR/<name>.npy in float64.  Above DUMP_MAX_BYTES in all, a
+    fixed seeded sample of the rows (the same rows of every array) is written, with their indices as rows.npy."""
+    os.makedirs(directory, exist_ok=True)
+    arrays = {k: np.asarray(v, dtype=np.float64) for k, v in arrays.items()}
+    n = len(next(iter(arrays.values())))
+    per_row = sum(a[:1].nbytes for a in arrays.values())
+    if per_row * n > DUMP_MAX_BYTES:
+        keep = max(1, (DUMP_MAX_BYTES - 8 * n) // (per_row + 8))
+        rows = np.sort(np.random.default_rng(0).choice(n, size=keep, replace=False))
+        arrays = {k: a[rows] for k, a in arrays.items()}
+        arrays["rows"] = rows.astype(np.float64)
+    for k, a in arrays.items():
+        np.save(os.path.join(directory, k + ".npy"), a)
+
+
 def spawn_ranks(n):
     """`python bench.py --gpus N` without a launcher: start the N ranks ourselves -- one process per GPU with the
     variables a launcher would export -- pass rank 0's line through and return the worst exit code."""
@@ -342,9 +372,14 @@ def main():
     ap.add_argument("--config", type=int, default=1, help="BASELINE configs[1] (default, the headline) | [2] | [3]")
     ap.add_argument("--snowpacks", type=int, default=0, help="snowpacks per GPU (default 1024 / 1024 / 512 by --config)")
     ap.add_argument("--threads", type=int, default=0, help="workgroup size of the per-pair kernels (0 = library default)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-secondary", action="store_true", help="skip the pcie_inclusive / model_run / other_configs measurements")
-    ap.add_argument("--no-other-configs", action="store_true", help="skip the short runs of configs[2] and configs[3] on the headline line")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also measure the per-kernel breakdown, HBM traffic (committed PMC summary), "
+                         "pcie_inclusive, model_run, the CPU baseline and the other configurations (default: headline only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed to DIR/<name>.npy (float64)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-secondary", action="store_true", help="with --full: skip the pcie_inclusive / model_run / other_configs measurements")
+    ap.add_argument("--no-other-configs", action="store_true", help="with --full: skip the short runs of configs[2] and configs[3] on the headline line")
     args = ap.parse_args()
     if args.steps is None:
         args.steps = {1: 20, 2: 5, 3: 3}.get(args.config, 20)
@@ -431,11 +466,17 @@ def main():
         allv = ctx.allreduce_max(mine)
         per_rank = {"kernel_ms": [float(v) for v in allv[:world]], "pairs": [int(v) for v in allv[world:]]}
 
-    # which kernel the time goes to: three more launches with an event pair around every kernel (outside the timed region)
-    res = ctx.download()
+    res = ctx.download()    # the last timed step's results
+    if args.dump_outputs and rank == 0:
+        if use_comm:        # what rank 0, the caller of the gather, receives: every rank's rows
+            dump_outputs(args.dump_outputs, {"values": gathered[0], "status": gathered[1]})
+        else:
+            dump_outputs(args.dump_outputs, {"values": res.values, "status": res.status, "layers": res.layers,
+                                             "streams": res.streams})
     info = ctx.launch_info()
     per_kernel = None
-    if not use_comm:
+    # (--full) which kernel the time goes to: three more launches with an event pair around every kernel (outside the timed region)
+    if args.full and not use_comm:
         # (one pipeline pass at a time for this: the intervals of concurrent passes overlap and would not add up)
         lanes_env = os.environ.get("SMRT_DORT_LANES")
         os.environ["SMRT_DORT_LANES"] = "1"
@@ -468,7 +509,7 @@ def main():
 
     traffic = None
     tpath = os.path.join(ROOT, "profiles", "hbm_traffic.json")
-    if os.path.exists(tpath):  # PMC counters cannot be collected from inside this process: measured with
+    if args.full and os.path.exists(tpath):  # PMC counters cannot be collected from inside this process: measured with
         with open(tpath) as fh:  # tools/pmc_passes.sh on the same command, summary committed under profiles/
             tj = json.load(fh)
         if args.config != 1:        # the other shapes: their own PMC passes (PMC_CONFIG=2|3 tools/pmc_passes.sh)
@@ -501,7 +542,7 @@ def main():
                                 "barrier + stream sync on both sides, max over ranks",
                 "value_is": "the resident-input rate (inputs in HBM when the timed region starts, as the bench contract asks); "
                             "SURVEY 8(d)'s rate including H2D of the packed inputs and D2H of the results is `pcie_inclusive` "
-                            "of this line, the plugin surface end to end is `model_run`",
+                            "of this line, the plugin surface end to end is `model_run` (both with --full)",
             },
             "roofline": {
                 "bound": "mfma",
@@ -538,15 +579,15 @@ def main():
                         "through HBM/L2 between its kernels (DESIGN.md 4), still far from HBM-bound",
             },
         }
-        if world == 1 and headline and not args.no_secondary:
+        if args.full and world == 1 and headline and not args.no_secondary:
             line["pcie_inclusive"] = pcie_inclusive(ctx, batch)
             line["model_run"] = model_run_rate(thick, dens, temp, lc, res.values)
-        if not args.no_cpu_baseline and world == 1 and headline:  # the CPU leg is reported at N = 1 only
+        if args.full and not args.no_cpu_baseline and world == 1 and headline:  # the CPU leg is reported at N = 1 only
             cb, err = cpu_baseline(thick, dens, temp, lc, res.values)
             line["cpu_baseline"] = cb
             line["config"]["max_abs_dTb_vs_oracle_K"] = err
         assert line["n_gpus"] == args.gpus
-        if world == 1 and not use_comm and headline and not args.no_secondary and not args.no_other_configs:
+        if args.full and world == 1 and not use_comm and headline and not args.no_secondary and not args.no_other_configs:
             # the other two BASELINE shapes, timed by whoever runs this command (short: 2 steps of configs[2] at 1024
             # snowpacks, 1 step of configs[3] at 512 -- their own contexts, this one's buffers released first)
             ctx.close()

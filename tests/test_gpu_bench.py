@@ -34,13 +34,17 @@ def _check_line(line, n_gpus):
     return d
 
 
-def test_bench_single_gpu_line():
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "1"],
-                         capture_output=True, text=True, timeout=600, cwd=ROOT)
+def test_bench_single_gpu_line(tmp_path):
+    """`--full`: the headline line with every secondary measurement; `--dump-outputs`: the last timed step's results."""
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "1", "--full",
+                          "--dump-outputs", str(tmp_path)], capture_output=True, text=True, timeout=600, cwd=ROOT)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]
     assert len(lines) == 1
     d = _check_line(lines[0], 1)
+    values, status = np.load(tmp_path / "values.npy"), np.load(tmp_path / "status.npy")
+    assert values.dtype == np.float64 and values.shape == (5120, 2, 1) and (status == 0).all()
+    assert np.isfinite(values).all() and 0.0 < values.min() and values.max() < 330.0     # brightness temperatures, K
     cb = d["cpu_baseline"]
     assert cb["kind"] == "port" and cb["cores"] >= 1 and cb["value"] > 0
     assert cb["blas_threads_per_worker"] == 1                      # measured inside the workers, not assumed
