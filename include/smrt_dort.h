@@ -443,6 +443,65 @@ int32_t smrt_dort_abi(int32_t* out, int32_t capacity);
 
 const char* smrt_dort_version(void);
 
+/*
+ * The iterative first-order backscatter solver (the reference's smrt/rtsolver/iterative_first_order.py: Ulaby et al. 2014
+ * eqs. 11.62, 11.74, 11.75; refraction factor of Tsang et al. 2007 eqs. 22a/b) on the same context.  Active sensors
+ * only, V and H, no atmosphere.  The batch is the smrt_batch of DORT: layers, kinds, wet snow, frequencies, theta (the
+ * incidence angles), the flat / reflector substrate (substrate_p1 / substrate_p2; the reflector IS allowed here) and the
+ * host_layer / host_iba_coeff scalars are read; n_max_stream, m_max, phase_normalization, prune_optical_depth,
+ * process_coherent_layers, the atmosphere, substrate_temperature, host_streams / host_phase, host_substrate* and
+ * host_interface* are ignored.  What this solver needs beyond it travels in the struct smrt_first_order_extras; NULL means Flat
+ * interfaces everywhere and no layer of kind SMRT_EM_HOST that scatters.  All arrays are indexed by the global pair f * S + s.
+ *   host_interface_slot   [F * S][n_layers_max + 1] int32, or NULL: entry l < n_layers is the interface ON TOP of layer l
+ *                         (0: the surface), entry n_layers the substrate; -1 = the device evaluates it (Flat interface;
+ *                         substrate_kind of the batch), k >= 0 = slot k of host_interface_values holds it;
+ *   host_interface_values [F * S][n_interface_slots][n_theta][10]: the caller's interface / substrate object evaluated at
+ *                         the cosine the incidence angle has in the medium ABOVE the boundary (Snell from the air):
+ *                         [0..1] specular reflection V, H; [2..3] coherent transmission downwards V, H; [4..5] coherent
+ *                         transmission upwards V, H (at the cosine in the medium below); [6..9] the 2 x 2 diffuse
+ *                         reflection at (mu, mu, azimuth pi), row-major.  A substrate leaves [2..5] zero;
+ *   host_phase_samples    [F * S][n_layers_max][n_theta][4][2][2], or NULL: for layers of kind SMRT_EM_HOST the phase
+ *                         matrix (V, H; NOT divided by 4 pi) at azimuth pi for (mu_s, mu_i) = (-mu, mu), (mu, -mu),
+ *                         (mu, mu), (-mu, -mu), mu the cosine of the incidence direction inside the layer.  Every other
+ *                         kind has its phase function on the device (IBA family, Rayleigh family, non-scattering).
+ * Outputs, one row per pair: out [4][n_theta][2][2] = the contributions order 0 (surface / interface / substrate
+ * backscatter), direct volume backscatter, double bounce, reflected backscatter as intensities (their sum x 4 pi cos
+ * theta is sigma0); status SMRT_OK or SMRT_ERR_INPUT (the row is NaN then); optional (may be NULL) layer_out
+ * [n_layers_max][5] as DORT's (column 4 is zero: no streams), backscatter_layer [n_layers_max + 1][n_theta][2][2] = what
+ * the surface (first) and every layer add, scaled by 4 pi x the cosine in the layer like the reference's other_data,
+ * diag [2] = largest single scattering albedo and total optical depth of the pair.
+ */
+typedef struct smrt_first_order_extras {
+    int32_t n_interface_slots;
+    int32_t reserved;
+    const int32_t* host_interface_slot;
+    const double* host_interface_values;
+    const double* host_phase_samples;
+} smrt_first_order_extras;
+
+/* Doubles per pair of `out`: 16 x n_theta. */
+int32_t smrt_first_order_out_stride(const smrt_batch* b);
+/* One shot over the listed pairs (semantics of smrt_dort_run_pairs; pairs == NULL: every pair of the batch in order,
+ * n_pairs ignored). */
+int32_t smrt_first_order_run_pairs(smrt_dort_ctx* ctx, const smrt_batch* batch, const smrt_first_order_extras* extras,
+                                   const int64_t* pairs, int64_t n_pairs, double* out, int32_t* status, double* layer_out,
+                                   double* backscatter_layer, double* diag);
+/* Split form: upload once, launch (asynchronous on the context's stream) any number of times, sync, download.  The
+ * upload returns when the copies are done: the caller's arrays may go away or change after it.  The optional outputs are
+ * always computed on the device; download copies the ones asked for (any of its pointers may be NULL).  One host thread
+ * per context, as for DORT. */
+int32_t smrt_first_order_upload_pairs(smrt_dort_ctx* ctx, const smrt_batch* batch, const smrt_first_order_extras* extras,
+                                      const int64_t* pairs, int64_t n_pairs);
+int32_t smrt_first_order_launch(smrt_dort_ctx* ctx);
+int32_t smrt_first_order_sync(smrt_dort_ctx* ctx);
+int32_t smrt_first_order_download(smrt_dort_ctx* ctx, double* out, int32_t* status, double* layer_out,
+                                  double* backscatter_layer, double* diag);
+/* HIP-event time (ms) of the two kernels of the last launch, after a sync: ms2[0] the per-(pair, layer) kernel, ms2[1]
+ * the per-(pair, angle) kernel. */
+int32_t smrt_first_order_kernel_ms(smrt_dort_ctx* ctx, double* ms2);
+/* Self-description of smrt_first_order_extras, like smrt_dort_abi: out[0] = its size, out[1..] = the field offsets. */
+int32_t smrt_first_order_abi(int32_t* out, int32_t capacity);
+
 #if defined(__GNUC__)
 #pragma GCC visibility pop
 #endif

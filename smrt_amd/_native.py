@@ -224,6 +224,69 @@ class PackedBatch:
         return (2, nt) if self.mode == "P" else (3, 3, nt)
 
 
+class FirstOrderExtras(C.Structure):
+    """struct smrt_first_order_extras of include/smrt_dort.h."""
+
+    _fields_ = [
+        ("n_interface_slots", C.c_int32),
+        ("reserved", C.c_int32),
+        ("host_interface_slot", C.POINTER(C.c_int32)),
+        ("host_interface_values", C.POINTER(C.c_double)),
+        ("host_phase_samples", C.POINTER(C.c_double)),
+    ]
+
+
+class PackedFirstOrderExtras:
+    """What the iterative first-order solver needs beyond a PackedBatch (include/smrt_dort.h: smrt_first_order_extras), for
+    a batch of `n_pairs` = F * S pairs, `n_layers_max` layers and `n_theta` incidence angles:
+    interfaces: None, or (slot [F*S][Lmax + 1] int (-1: evaluated on the device; entry n_layers of a snowpack: its substrate),
+        values [F*S][slots][n_theta][10]) for the interfaces / substrates evaluated by the caller;
+    phase_samples: None, or [F*S][Lmax][n_theta][4][2][2] for the layers of kind "host"."""
+
+    def __init__(self, n_pairs, n_layers_max, n_theta, interfaces=None, phase_samples=None):
+        x = FirstOrderExtras()
+        FS, L, T = int(n_pairs), int(n_layers_max), int(n_theta)
+        if interfaces is not None:
+            slot = np.asarray(interfaces[0], dtype=np.int32)
+            if slot.size != FS * (L + 1):
+                raise SMRTError("the interface slot table must have the shape (n_pairs, n_layers_max + 1)")
+            self.slot = np.ascontiguousarray(slot.reshape(FS, L + 1))
+            values = np.asarray(interfaces[1], np.float64)
+            if values.size == 0 or values.size % (FS * T * 10):
+                raise SMRTError("the interface values must have the shape (n_pairs, slots, n_theta, 10)")
+            nslots = values.size // (FS * T * 10)
+            if self.slot.min() < -1 or self.slot.max() >= nslots:
+                raise SMRTError("interface slot out of range")
+            self.values = np.ascontiguousarray(values.reshape(FS, nslots, T, 10))
+            x.n_interface_slots = nslots
+            x.host_interface_slot = self.slot.ctypes.data_as(C.POINTER(C.c_int32))
+            x.host_interface_values = _dptr(self.values)
+        if phase_samples is not None:
+            ph = np.asarray(phase_samples, np.float64)
+            if ph.size != FS * L * T * 16:
+                raise SMRTError("the phase samples must have the shape (n_pairs, n_layers_max, n_theta, 4, 2, 2)")
+            self.phase_samples = np.ascontiguousarray(ph.reshape(FS, L, T, 4, 2, 2))
+            x.host_phase_samples = _dptr(self.phase_samples)
+        self.struct = x
+
+
+class FirstOrderOutput:
+    """Outputs of the first-order solver for `pair_count` pairs: values [4 contributions][n_theta][2][2], status, layers
+    [Lmax][5], layer_backscatter [Lmax + 1][n_theta][2][2], diag (largest albedo, optical depth)."""
+
+    def __init__(self, batch, pair_count):
+        Lmax, nt = int(batch.struct.n_layers_max), int(batch.struct.n_theta)
+        self.values = np.empty((pair_count, 4, nt, 2, 2))
+        self.status = np.empty(pair_count, dtype=np.int32)
+        self.layers = np.empty((pair_count, Lmax, 5))
+        self.layer_backscatter = np.empty((pair_count, Lmax + 1, nt, 2, 2))
+        self.diag = np.empty((pair_count, 2))
+
+    def pointers(self):
+        return (_dptr(self.values), self.status.ctypes.data_as(C.POINTER(C.c_int32)), _dptr(self.layers),
+                _dptr(self.layer_backscatter), _dptr(self.diag))
+
+
 _lib = None
 
 
@@ -315,6 +378,24 @@ def load_library():
     lib.smrt_dort_device_count.restype = C.c_int32
     lib.smrt_gauss_legendre_positive.argtypes = [C.c_int32, P(C.c_double), P(C.c_double)]
     lib.smrt_gauss_legendre_positive.restype = C.c_int32
+    X = P(FirstOrderExtras)
+    lib.smrt_first_order_out_stride.argtypes = [P(SmrtBatch)]
+    lib.smrt_first_order_out_stride.restype = C.c_int32
+    lib.smrt_first_order_run_pairs.argtypes = [C.c_void_p, P(SmrtBatch), X, P(C.c_int64), C.c_int64, P(C.c_double), P(C.c_int32),
+                                               P(C.c_double), P(C.c_double), P(C.c_double)]
+    lib.smrt_first_order_run_pairs.restype = C.c_int32
+    lib.smrt_first_order_upload_pairs.argtypes = [C.c_void_p, P(SmrtBatch), X, P(C.c_int64), C.c_int64]
+    lib.smrt_first_order_upload_pairs.restype = C.c_int32
+    lib.smrt_first_order_launch.argtypes = [C.c_void_p]
+    lib.smrt_first_order_launch.restype = C.c_int32
+    lib.smrt_first_order_sync.argtypes = [C.c_void_p]
+    lib.smrt_first_order_sync.restype = C.c_int32
+    lib.smrt_first_order_download.argtypes = [C.c_void_p, P(C.c_double), P(C.c_int32), P(C.c_double), P(C.c_double), P(C.c_double)]
+    lib.smrt_first_order_download.restype = C.c_int32
+    lib.smrt_first_order_kernel_ms.argtypes = [C.c_void_p, P(C.c_double)]
+    lib.smrt_first_order_kernel_ms.restype = C.c_int32
+    lib.smrt_first_order_abi.argtypes = [P(C.c_int32), C.c_int32]
+    lib.smrt_first_order_abi.restype = C.c_int32
     check_struct_layout(lib)
     _lib = lib
     return lib
@@ -336,6 +417,23 @@ def check_struct_layout(lib):
     if mine != theirs:
         raise SMRTError(f"smrt_batch layout mismatch between smrt_amd/_native.py {mine} and {LIB_PATH} {theirs}: "
                         "rebuild the library or update the binding (include/smrt_dort.h)")
+    mine, theirs = first_order_extras_layout(), first_order_abi_layout(lib)
+    if mine != theirs:
+        raise SMRTError(f"smrt_first_order_extras layout mismatch between smrt_amd/_native.py {mine} and {LIB_PATH} {theirs}: "
+                        "rebuild the library or update the binding (include/smrt_dort.h)")
+
+
+def first_order_extras_layout():
+    """[sizeof, field offsets] of the ctypes declaration of smrt_first_order_extras."""
+    return [C.sizeof(FirstOrderExtras)] + [getattr(FirstOrderExtras, name).offset for name, _ in FirstOrderExtras._fields_]
+
+
+def first_order_abi_layout(lib):
+    """The same as the library was compiled (smrt_first_order_abi)."""
+    n = lib.smrt_first_order_abi(None, 0)
+    a = (C.c_int32 * n)()
+    lib.smrt_first_order_abi(a, n)
+    return list(a)
 
 
 EXPORTED_SYMBOLS = [
@@ -345,6 +443,8 @@ EXPORTED_SYMBOLS = [
     "smrt_dort_comm_allreduce_max", "smrt_dort_launch", "smrt_dort_sync", "smrt_dort_download", "smrt_dort_last_kernel_ms", "smrt_dort_kernel_breakdown",
     "smrt_dort_total_kernel_ms", "smrt_dort_set_block_threads", "smrt_dort_set_pipeline", "smrt_dort_set_diagonalisation", "smrt_dort_sum_n3", "smrt_dort_stage_cycles", "smrt_dort_device_count", "smrt_gauss_legendre_positive",
     "smrt_dort_version", "smrt_dort_finish_reg_lds_bytes", "smrt_dort_finish_strip_lds_bytes", "smrt_dort_jacobi_lds_bytes", "smrt_dort_gather_plan",
+    "smrt_first_order_out_stride", "smrt_first_order_run_pairs", "smrt_first_order_upload_pairs", "smrt_first_order_launch",
+    "smrt_first_order_sync", "smrt_first_order_download", "smrt_first_order_kernel_ms", "smrt_first_order_abi",
 ]
 
 
@@ -451,6 +551,67 @@ class DortContext:
         self._check(self._lib.smrt_dort_download(self._h, _dptr(o.values), o.status.ctypes.data_as(C.POINTER(C.c_int32)),
                                                  _dptr(o.layers), _dptr(o.streams)), "smrt_dort_download")
         return o
+
+    # ---- the iterative first-order solver (smrt_first_order_*) ----------------------------------------------------
+    @staticmethod
+    def _first_order_args(batch, extras, pairs):
+        if pairs is not None:
+            pairs = np.ascontiguousarray(pairs, dtype=np.int64)
+        return (C.byref(batch.struct), C.byref(extras.struct) if extras is not None else None,
+                pairs.ctypes.data_as(C.POINTER(C.c_int64)) if pairs is not None else None,
+                len(pairs) if pairs is not None else -1), pairs
+
+    def first_order_run(self, batch: PackedBatch, extras=None, pairs=None) -> FirstOrderOutput:
+        """One shot (H2D, two kernels, D2H) for every pair of the batch or the listed ones (row i = pairs[i])."""
+        args, pairs = self._first_order_args(batch, extras, pairs)
+        o = FirstOrderOutput(batch, batch.n_pairs if pairs is None else len(pairs))
+        with self.lock:
+            self._check(self._lib.smrt_first_order_run_pairs(self._h, *args, *o.pointers()), "smrt_first_order_run_pairs")
+        return o
+
+    def first_order_upload(self, batch: PackedBatch, extras=None, pairs=None):
+        """Split form (upload once, launch any number of times, sync, download).  Every call takes the context's lock,
+        but the resident batch belongs to the context: a thread that uses the split form must hold `self.lock` from its
+        upload to its download if another thread may solve on the same (cached) context meanwhile."""
+        args, pairs = self._first_order_args(batch, extras, pairs)
+        with self.lock:
+            self._check(self._lib.smrt_first_order_upload_pairs(self._h, *args), "smrt_first_order_upload_pairs")
+            self._first_order_resident = (batch, extras, pairs, batch.n_pairs if pairs is None else len(pairs))
+
+    def first_order_launch(self):
+        with self.lock:
+            self._check(self._lib.smrt_first_order_launch(self._h), "smrt_first_order_launch")
+
+    def first_order_sync(self):
+        with self.lock:
+            self._check(self._lib.smrt_first_order_sync(self._h), "smrt_first_order_sync")
+
+    def first_order_download(self, layers_only=False) -> FirstOrderOutput:
+        """The outputs of the last launch; layers_only: only `layers` (and `status`) are copied back, the other arrays of
+        the returned object are left unset."""
+        with self.lock:
+            batch, _, _, n = self._first_order_resident
+            o = FirstOrderOutput(batch, n)
+            ptrs = o.pointers()
+            if layers_only:
+                ptrs = (None, ptrs[1], ptrs[2], None, None)
+                o.values = o.layer_backscatter = o.diag = None
+            self._check(self._lib.smrt_first_order_download(self._h, *ptrs), "smrt_first_order_download")
+        return o
+
+    def first_order_layers(self, batch: PackedBatch):
+        """[n_pairs, Lmax, 5] layer scalars (Re eps, Im eps, ks, ka, 0) of every pair of the batch as the device computes
+        them: one run of the solver without extras of which only layer_out is copied back."""
+        with self.lock:
+            self.first_order_upload(batch)
+            self.first_order_launch()
+            return self.first_order_download(layers_only=True).layers
+
+    def first_order_kernel_ms(self):
+        """HIP-event ms of the (pair, layer) kernel and of the (pair, angle) kernel of the last launch."""
+        a = np.zeros(2)
+        self._check(self._lib.smrt_first_order_kernel_ms(self._h, _dptr(a)), "smrt_first_order_kernel_ms")
+        return float(a[0]), float(a[1])
 
     def ft_even_phase(self, emmodel, microstructure, frequency, frac_volume, temperature, p1, p2, mu_s, mu_i, m_max, npol):
         """Azimuthal modes of the phase matrix of one layer: array [npol, npol, m_max + 1, len(mu_s), len(mu_i)]."""

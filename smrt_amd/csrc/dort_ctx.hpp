@@ -84,6 +84,8 @@ struct smrt_dort_ctx {
     void* comm = nullptr;
     int comm_world = 0, comm_rank = 0;
     DevBuf d_gather_out, d_gather_status, d_scalar;
+    // the iterative first-order solver (first_order.hip): its own buffers and resident batch, made on first use
+    struct FirstOrderState* first_order = nullptr;
 };
 
 #ifndef SMRT_JACOBI_NT
@@ -128,4 +130,6 @@ hipError_t ft_even_phase(smrt_dort_ctx* ctx, const smrt::PhaseRequest& q);
 hipError_t prune_mark(smrt_dort_ctx* ctx, const smrt::DevBatch& c, int* done_dev);
 // k_cost.hip: sum of N_l^3 per pair from the stream counts alone
 hipError_t pair_cost(smrt_dort_ctx* ctx, const smrt::DevBatch& d, double* cost_dev);
+// first_order.hip: frees ctx->first_order (smrt_dort_destroy)
+void first_order_release(smrt_dort_ctx* ctx);
 }  // namespace smrt_launch

@@ -22,6 +22,19 @@ class GeometricalOpticsBackscatter(GeometricalOptics):
                 gamma = gamma / (1 + shadowing(s2, 1 / np.sqrt(tan2)))
         return gamma
 
+    def diffuse_reflection_matrix(self, frequency, eps_1, eps_2, mu_s, mu_i, dphi, npol):
+        """In the backscatter geometry (mu_s = mu_i, the single azimuth pi) -- what the iterative first-order solver asks --
+        [npol, len(mu_i)]: the closed-form backscatter itself, the same in V and H, consistent with this class's
+        ft_even_diffuse_reflection_matrix (smrt/interface/geometrical_optics_backscatter.py:47-99).  Any other geometry
+        keeps the bistatic matrix of the full geometrical-optics model this class inherits (the reference refuses those)."""
+        mu_s, mu_i = np.atleast_1d(np.asarray(mu_s, float)), np.atleast_1d(np.asarray(mu_i, float))
+        if mu_s.shape != mu_i.shape or not np.allclose(mu_s, mu_i) or np.size(dphi) != 1 or not np.allclose(dphi, np.pi):
+            return super().diffuse_reflection_matrix(frequency, eps_1, eps_2, mu_s, mu_i, dphi, npol)
+        gamma = self.backscatter(eps_1, eps_2, mu_i)
+        out = np.zeros((npol, len(gamma)))
+        out[:2] = gamma
+        return out
+
     def ft_even_diffuse_reflection_matrix(self, frequency, eps_1, eps_2, mu_s, mu_i, m_max, npol):
         """[npol, m_max + 1, len(mu_i)], diagonal in the streams; modes weighted 1, -2, +2, ... over 1 + 2 m_max."""
         if not np.allclose(mu_s, mu_i):

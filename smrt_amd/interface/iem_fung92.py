@@ -94,6 +94,16 @@ class IEM_Fung92(KirchhoffCoherentPart):
             out[row] = front * np.sum(weight * (series.real ** 2 + series.imag ** 2), axis=0) / (4 * np.pi * mu)
         return out
 
+    def diffuse_reflection_matrix(self, frequency, eps_1, eps_2, mu_s, mu_i, dphi, npol):
+        """[npol, len(mu_i)]: the backscatter itself (mu_s = mu_i, dphi = pi), diagonal in the polarisation -- what the
+        iterative first-order solver asks (smrt/interface/iem_fung92.py:88-177)."""
+        if not np.allclose(mu_s, mu_i) or np.size(dphi) != 1 or not np.allclose(dphi, np.pi):
+            raise NotImplementedError("Only the backscattering coefficient is implemented at this stage in iem_fung92.")
+        gamma = self.backscatter(frequency, eps_1, eps_2, mu_i)
+        out = np.zeros((npol, gamma.shape[1]))
+        out[:2] = gamma
+        return out
+
     def ft_even_diffuse_reflection_matrix(self, frequency, eps_1, eps_2, mu_s, mu_i, m_max, npol):
         """[npol, m_max + 1, len(mu_i)]: diagonal in the streams (backscatter only, mu_s must equal mu_i); the energy of the
         backscatter lobe is spread over the azimuth modes: coefficient 1, -2, +2, -2 ... over 1 + 2 m_max

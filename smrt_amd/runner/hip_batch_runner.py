@@ -38,8 +38,11 @@ class HipBatchRunner(object):
             options.setdefault("block_threads", self.block_threads)
             try:
                 rtsolver = rtsolver(**options)
-            except TypeError:  # an rtsolver that does not know smrt_amd's own knobs
-                rtsolver = model.rtsolver(**model.rtsolver_options)
+            except TypeError:
+                try:    # an rtsolver with a device list but one kernel shape (iterative_first_order)
+                    rtsolver = model.rtsolver(**{k: v for k, v in options.items() if k != "block_threads" or k in model.rtsolver_options})
+                except TypeError:  # an rtsolver that does not know smrt_amd's own knobs
+                    rtsolver = model.rtsolver(**model.rtsolver_options)
         return rtsolver
 
     def run_plan(self, model, plan):

@@ -27,5 +27,10 @@ class InterfaceSubstrate(SubstrateBase):
     def emissivity_matrix(self, frequency, eps_1, mu1, npol):
         return self.interface.coherent_transmission_matrix(frequency, eps_1, self._below(frequency), mu1, npol)
 
+    def diffuse_reflection_matrix(self, frequency, eps_1, mu_s, mu_i, dphi, npol):
+        if not callable(getattr(self.interface, "diffuse_reflection_matrix", None)):
+            return 0.0
+        return self.interface.diffuse_reflection_matrix(frequency, eps_1, self._below(frequency), mu_s, mu_i, dphi, npol)
+
     def ft_even_diffuse_reflection_matrix(self, frequency, eps_1, mu_s, mu_i, m_max, npol):
         return self.interface.ft_even_diffuse_reflection_matrix(frequency, eps_1, self._below(frequency), mu_s, mu_i, m_max, npol)

@@ -32,6 +32,8 @@ def ctype_of(decl):
         return "C.POINTER(SmrtBatch)"
     if base == "smrt_gather_op":   # {int32 peer, int32 reserved, int64 offset_rows, int64 rows}: passed as an opaque array
         return "C.c_void_p"
+    if base == "smrt_first_order_extras":   # {int32 slots, int32 reserved, three pointers}: optional, passed as an opaque pointer (or None)
+        return "C.c_void_p"
     c = SCALARS[base]
     for _ in range(stars):
         c = "C.POINTER(%s)" % c
