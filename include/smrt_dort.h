@@ -502,6 +502,55 @@ int32_t smrt_first_order_kernel_ms(smrt_dort_ctx* ctx, double* ms2);
 /* Self-description of smrt_first_order_extras, like smrt_dort_abi: out[0] = its size, out[1..] = the field offsets. */
 int32_t smrt_first_order_abi(int32_t* out, int32_t capacity);
 
+/*
+ * The successive-order-of-scattering solver (the reference's smrt/rtsolver/successive_order.py: Lenoble et al. 2007 eq. 66,
+ * Greenwald et al. 2005 eq. 2) on the same context.  Passive sensors only, Flat interfaces, no atmosphere, emmodels with a
+ * device implementation.  The batch is the smrt_batch of DORT: layers, kinds, wet snow, frequencies, theta, n_max_stream
+ * (2 to 64), rayleigh_jeans, the flat / reflector substrate with its temperature (its own emission (1 - R) B(T) enters order
+ * 0) are read; m_max only sets the number of azimuth samples of the phase function, as in the reference;
+ * phase_normalization and prune_optical_depth are ignored; an atmosphere, host_* arrays, process_coherent_layers and layer
+ * kinds evaluated by the caller are refused.  No new struct: the two options of the solver are arguments.
+ *   n_iteration_max     orders computed at most (order 0 = emission alone);
+ *   relative_tolerance  the loop stops after storing the first order whose largest emerging radiance (air streams, V and
+ *                       H) is below relative_tolerance x that of order 0; later orders are exactly 0;
+ *   workspace_budget_bytes  everything the solver reserves on the device for this batch stays inside it (<= 0: 8 GiB):
+ *                       inputs, per-layer tables, outputs, and per chunk of pairs the weighted phase matrices
+ *                       (n_layers_max x (16-padded 4 n_max_stream)^2 doubles per pair) and the workspace (radiance
+ *                       profile and source: (2 K + L) x padded directions per pair, K its sublayers).  The launch solves
+ *                       chunk after chunk.  A pair that does not fit alone gets SMRT_ERR_DEPTH; a budget smaller than
+ *                       the buffers of the batch itself fails the upload.
+ * Outputs, one row per pair: out [n_iteration_max + 1][2][n_theta] kelvin (V, H): every order through the inverse Planck
+ * function by itself, last the total = inverse Planck of the summed radiances; status SMRT_OK, SMRT_ERR_INPUT or
+ * SMRT_ERR_DEPTH (the row is NaN then); optional (may be NULL) layer_out [n_layers_max][5] and streams [1 + n_max_stream] as
+ * DORT's, sublayers [n_layers_max] int32, max_radiance [n_iteration_max] (largest emerging radiance of every order run, 0
+ * after the stop), orders [1] int32 (orders run).
+ */
+#define SMRT_ERR_DEPTH 7
+/* Doubles per pair of `out`: (n_iteration_max + 1) x 2 x n_theta. */
+int32_t smrt_successive_order_out_stride(const smrt_batch* b, int32_t n_iteration_max);
+/* One shot over the listed pairs (semantics of smrt_dort_run_pairs; pairs == NULL: every pair of the batch in order,
+ * n_pairs ignored). */
+int32_t smrt_successive_order_run_pairs(smrt_dort_ctx* ctx, const smrt_batch* batch, int32_t n_iteration_max,
+                                        double relative_tolerance, int64_t workspace_budget_bytes, const int64_t* pairs,
+                                        int64_t n_pairs, double* out, int32_t* status, double* layer_out, double* streams,
+                                        int32_t* sublayers, double* max_radiance, int32_t* orders);
+/* Split form: upload once, launch any number of times, sync, download.  The upload returns when the copies are done.  The
+ * launch reads the sublayer counts back after its first kernel (they size the chunks) and is asynchronous from there on.
+ * One host thread per context, as for DORT. */
+int32_t smrt_successive_order_upload_pairs(smrt_dort_ctx* ctx, const smrt_batch* batch, int32_t n_iteration_max,
+                                           double relative_tolerance, int64_t workspace_budget_bytes, const int64_t* pairs,
+                                           int64_t n_pairs);
+int32_t smrt_successive_order_launch(smrt_dort_ctx* ctx);
+int32_t smrt_successive_order_sync(smrt_dort_ctx* ctx);
+int32_t smrt_successive_order_download(smrt_dort_ctx* ctx, double* out, int32_t* status, double* layer_out, double* streams,
+                                       int32_t* sublayers, double* max_radiance, int32_t* orders);
+/* HIP-event time (ms) of the last launch, after a sync: ms2[0] the two preparation kernels, ms2[1] the sweep kernel, each
+ * summed over the chunks. */
+int32_t smrt_successive_order_kernel_ms(smrt_dort_ctx* ctx, double* ms2);
+/* The last launch: info[0] = chunks, info[1] = bytes reserved (all buffers), info[2] = pairs over the budget, info[3] = the
+ * budget.  Returns the number of entries; at most `capacity` are written. */
+int32_t smrt_successive_order_launch_info(smrt_dort_ctx* ctx, int64_t* info, int32_t capacity);
+
 #if defined(__GNUC__)
 #pragma GCC visibility pop
 #endif

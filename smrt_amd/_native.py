@@ -36,6 +36,7 @@ STATUS_MESSAGES = {
     5: "Invalid layer properties (temperature above the freezing point, fewer than two streams in a layer, or -- for an "
        "emmodel evaluated on the host -- a negative ka / permittivity or a stream count that differs from the device's).",
     6: "process_coherent_layers: the last layer is coherent, or two successive layers are coherent; this is not supported.",
+    7: "snowpack optically too deep for the successive_order workspace: N sublayers",
 }
 
 
@@ -287,6 +288,31 @@ class FirstOrderOutput:
                 _dptr(self.layer_backscatter), _dptr(self.diag))
 
 
+class SuccessiveOrderOutput:
+    """Outputs of the successive-order solver for `pair_count` pairs: values [2][n_theta][n_iteration_max + 1] kelvin (the
+    last entry of the order axis is the total), status, layers [Lmax][5] and streams [1 + n_max_stream] as DORT's, sublayers
+    [Lmax], max_radiance [n_iteration_max] (largest emerging radiance of every order run), orders (orders run)."""
+
+    def __init__(self, batch, pair_count, n_iteration_max):
+        Lmax, nt, nmax = int(batch.struct.n_layers_max), int(batch.struct.n_theta), int(batch.struct.n_max_stream)
+        self.raw = np.empty((pair_count, n_iteration_max + 1, 2, nt))   # as the device writes it
+        self.status = np.empty(pair_count, dtype=np.int32)
+        self.layers = np.empty((pair_count, Lmax, 5))
+        self.streams = np.empty((pair_count, 1 + nmax))
+        self.sublayers = np.empty((pair_count, Lmax), dtype=np.int32)
+        self.max_radiance = np.empty((pair_count, n_iteration_max))
+        self.orders = np.empty(pair_count, dtype=np.int32)
+
+    @property
+    def values(self):
+        return np.moveaxis(self.raw, 1, 3)
+
+    def pointers(self):
+        i32 = lambda a: a.ctypes.data_as(C.POINTER(C.c_int32))  # noqa: E731
+        return (_dptr(self.raw), i32(self.status), _dptr(self.layers), _dptr(self.streams), i32(self.sublayers),
+                _dptr(self.max_radiance), i32(self.orders))
+
+
 _lib = None
 
 
@@ -396,6 +422,23 @@ def load_library():
     lib.smrt_first_order_kernel_ms.restype = C.c_int32
     lib.smrt_first_order_abi.argtypes = [P(C.c_int32), C.c_int32]
     lib.smrt_first_order_abi.restype = C.c_int32
+    so_out = [P(C.c_double), P(C.c_int32), P(C.c_double), P(C.c_double), P(C.c_int32), P(C.c_double), P(C.c_int32)]
+    lib.smrt_successive_order_out_stride.argtypes = [P(SmrtBatch), C.c_int32]
+    lib.smrt_successive_order_out_stride.restype = C.c_int32
+    lib.smrt_successive_order_run_pairs.argtypes = [C.c_void_p, P(SmrtBatch), C.c_int32, C.c_double, C.c_int64, P(C.c_int64), C.c_int64] + so_out
+    lib.smrt_successive_order_run_pairs.restype = C.c_int32
+    lib.smrt_successive_order_upload_pairs.argtypes = [C.c_void_p, P(SmrtBatch), C.c_int32, C.c_double, C.c_int64, P(C.c_int64), C.c_int64]
+    lib.smrt_successive_order_upload_pairs.restype = C.c_int32
+    lib.smrt_successive_order_launch.argtypes = [C.c_void_p]
+    lib.smrt_successive_order_launch.restype = C.c_int32
+    lib.smrt_successive_order_sync.argtypes = [C.c_void_p]
+    lib.smrt_successive_order_sync.restype = C.c_int32
+    lib.smrt_successive_order_download.argtypes = [C.c_void_p] + so_out
+    lib.smrt_successive_order_download.restype = C.c_int32
+    lib.smrt_successive_order_kernel_ms.argtypes = [C.c_void_p, P(C.c_double)]
+    lib.smrt_successive_order_kernel_ms.restype = C.c_int32
+    lib.smrt_successive_order_launch_info.argtypes = [C.c_void_p, P(C.c_int64), C.c_int32]
+    lib.smrt_successive_order_launch_info.restype = C.c_int32
     check_struct_layout(lib)
     _lib = lib
     return lib
@@ -445,6 +488,9 @@ EXPORTED_SYMBOLS = [
     "smrt_dort_version", "smrt_dort_finish_reg_lds_bytes", "smrt_dort_finish_strip_lds_bytes", "smrt_dort_jacobi_lds_bytes", "smrt_dort_gather_plan",
     "smrt_first_order_out_stride", "smrt_first_order_run_pairs", "smrt_first_order_upload_pairs", "smrt_first_order_launch",
     "smrt_first_order_sync", "smrt_first_order_download", "smrt_first_order_kernel_ms", "smrt_first_order_abi",
+    "smrt_successive_order_out_stride", "smrt_successive_order_run_pairs", "smrt_successive_order_upload_pairs",
+    "smrt_successive_order_launch", "smrt_successive_order_sync", "smrt_successive_order_download",
+    "smrt_successive_order_kernel_ms", "smrt_successive_order_launch_info",
 ]
 
 
@@ -612,6 +658,64 @@ class DortContext:
         a = np.zeros(2)
         self._check(self._lib.smrt_first_order_kernel_ms(self._h, _dptr(a)), "smrt_first_order_kernel_ms")
         return float(a[0]), float(a[1])
+
+    # ---- the successive-order solver (smrt_successive_order_*) ----------------------------------------------------
+    @staticmethod
+    def _successive_order_args(batch, n_iteration_max, relative_tolerance, workspace_budget, pairs):
+        if pairs is not None:
+            pairs = np.ascontiguousarray(pairs, dtype=np.int64)
+        return (C.byref(batch.struct), int(n_iteration_max), float(relative_tolerance), int(workspace_budget or 0),
+                pairs.ctypes.data_as(C.POINTER(C.c_int64)) if pairs is not None else None,
+                len(pairs) if pairs is not None else -1), pairs
+
+    def successive_order_run(self, batch: PackedBatch, n_iteration_max=50, relative_tolerance=0.001, pairs=None,
+                             workspace_budget=None) -> SuccessiveOrderOutput:
+        """One shot (H2D, kernels chunk after chunk, D2H) for every pair of the batch or the listed ones (row i = pairs[i]).
+        workspace_budget: bytes everything reserved on the device stays inside (None: the library's default)."""
+        args, pairs = self._successive_order_args(batch, n_iteration_max, relative_tolerance, workspace_budget, pairs)
+        o = SuccessiveOrderOutput(batch, batch.n_pairs if pairs is None else len(pairs), int(n_iteration_max))
+        with self.lock:
+            self._check(self._lib.smrt_successive_order_run_pairs(self._h, *args, *o.pointers()), "smrt_successive_order_run_pairs")
+        return o
+
+    def successive_order_upload(self, batch: PackedBatch, n_iteration_max=50, relative_tolerance=0.001, pairs=None,
+                                workspace_budget=None):
+        """Split form (upload once, launch any number of times, sync, download); see first_order_upload for the lock."""
+        args, pairs = self._successive_order_args(batch, n_iteration_max, relative_tolerance, workspace_budget, pairs)
+        with self.lock:
+            self._check(self._lib.smrt_successive_order_upload_pairs(self._h, *args), "smrt_successive_order_upload_pairs")
+            self._successive_order_resident = (batch, pairs, batch.n_pairs if pairs is None else len(pairs), int(n_iteration_max))
+
+    def successive_order_launch(self):
+        with self.lock:
+            self._check(self._lib.smrt_successive_order_launch(self._h), "smrt_successive_order_launch")
+
+    def successive_order_sync(self):
+        with self.lock:
+            self._check(self._lib.smrt_successive_order_sync(self._h), "smrt_successive_order_sync")
+
+    def successive_order_download(self) -> SuccessiveOrderOutput:
+        with self.lock:
+            batch, _, n, n_it = self._successive_order_resident
+            o = SuccessiveOrderOutput(batch, n, n_it)
+            self._check(self._lib.smrt_successive_order_download(self._h, *o.pointers()), "smrt_successive_order_download")
+        return o
+
+    def successive_order_kernel_ms(self):
+        """HIP-event ms of the preparation kernels and of the sweep kernel of the last launch (summed over its chunks)."""
+        a = np.zeros(2)
+        with self.lock:
+            self._check(self._lib.smrt_successive_order_kernel_ms(self._h, _dptr(a)), "smrt_successive_order_kernel_ms")
+        return float(a[0]), float(a[1])
+
+    def successive_order_launch_info(self):
+        """dict(chunks, reserved_bytes, over_budget, budget) of the last launch."""
+        a = np.zeros(4, dtype=np.int64)
+        with self.lock:
+            # (returns the number of entries it has, -1 on error)
+            self._check(int(self._lib.smrt_successive_order_launch_info(self._h, a.ctypes.data_as(C.POINTER(C.c_int64)), 4) < 0),
+                        "smrt_successive_order_launch_info")
+        return dict(chunks=int(a[0]), reserved_bytes=int(a[1]), over_budget=int(a[2]), budget=int(a[3]))
 
     def ft_even_phase(self, emmodel, microstructure, frequency, frac_volume, temperature, p1, p2, mu_s, mu_i, m_max, npol):
         """Azimuthal modes of the phase matrix of one layer: array [npol, npol, m_max + 1, len(mu_s), len(mu_i)]."""

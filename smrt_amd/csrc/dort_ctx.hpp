@@ -86,6 +86,8 @@ struct smrt_dort_ctx {
     DevBuf d_gather_out, d_gather_status, d_scalar;
     // the iterative first-order solver (first_order.hip): its own buffers and resident batch, made on first use
     struct FirstOrderState* first_order = nullptr;
+    // the successive-order solver (successive_order.hip): likewise
+    struct SuccessiveOrderState* successive_order = nullptr;
 };
 
 #ifndef SMRT_JACOBI_NT
@@ -132,4 +134,6 @@ hipError_t prune_mark(smrt_dort_ctx* ctx, const smrt::DevBatch& c, int* done_dev
 hipError_t pair_cost(smrt_dort_ctx* ctx, const smrt::DevBatch& d, double* cost_dev);
 // first_order.hip: frees ctx->first_order (smrt_dort_destroy)
 void first_order_release(smrt_dort_ctx* ctx);
+// successive_order.hip: frees ctx->successive_order (smrt_dort_destroy)
+void successive_order_release(smrt_dort_ctx* ctx);
 }  // namespace smrt_launch

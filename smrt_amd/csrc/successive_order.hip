@@ -1,0 +1,353 @@
+// The successive-order-of-scattering solver of libsmrt_dort.so (include/smrt_dort.h: smrt_successive_order_*): its three
+// kernels -- one lane per (pair, layer) for the layer electromagnetics, one workgroup per (pair, layer) for the streams,
+// interface coefficients and the weighted phase matrix, one workgroup per pair for all the orders; arithmetic in
+// successive_order_kernel.hpp -- and the host side: buffers on the DORT context, the chunk plan that keeps everything
+// inside one budget, upload / launch / sync / download and the one-shot call.
+#include <hip/hip_runtime.h>
+#include <cmath>
+#include <cstddef>
+#include <cstring>
+#include <string>
+#include <vector>
+
+#include "dort_ctx.hpp"
+#include "dort_host_common.hpp"
+#include "successive_order_kernel.hpp"
+#include "../../include/smrt_dort.h"
+
+using namespace smrt;
+
+#define HIPCHK(call)                                                                              \
+    do {                                                                                          \
+        hipError_t e_ = (call);                                                                   \
+        if (e_ != hipSuccess) {                                                                   \
+            ctx->err = std::string(#call) + ": " + hipGetErrorString(e_);                         \
+            return -1;                                                                            \
+        }                                                                                         \
+    } while (0)
+
+__global__ void __launch_bounds__(kSoThreads) successive_order_layers_kernel(SoBatch b) {
+    const long long idx = (long long)blockIdx.x * kSoThreads + threadIdx.x;
+    if (idx >= b.n_pairs * b.Lmax) return;
+    so_layer_item(b, idx % b.n_pairs, (int)(idx / b.n_pairs));   // pairs fastest: the staging rows are written with unit stride
+}
+
+__global__ void __launch_bounds__(kSoThreads) successive_order_prep_kernel(SoBatch b) {
+    const long long item = blockIdx.x;   // layers fastest: the Wt matrices of a pair are written next to each other
+    so_prep_item<kSoThreads>(b, b.chunk_begin + item / b.Lmax, (int)(item % b.Lmax));
+}
+
+__global__ void __launch_bounds__(kSoThreads) successive_order_sweep_kernel(SoBatch b) {
+    extern __shared__ double so_lds[];
+    so_sweep_pair<kSoThreads>(b, b.chunk_begin + blockIdx.x, so_lds);
+}
+
+struct SuccessiveOrderState {
+    DevBuf nl, thick, fv, temp, p1, p2, freq, theta, lw, kind, sub1, sub2, subT, gl, pairmap;
+    DevBuf stage, nsub, nstream, vec, srcterm, wsoff, chunk, out, status, layer, streams, maxrad, orders;
+    SoBatch dev{};
+    bool uploaded = false, launched = false;
+    int64_t budget = 0;
+    size_t fixed_bytes = 0;             // everything reserved but the chunk buffer
+    size_t chunk_bytes = 0;             // the chunk buffer (Wt + workspace of the largest chunk)
+    std::vector<int32_t> nsub_host;     // [n_pairs][Lmax] after a launch
+    std::vector<long long> deep;        // rows that do not fit the budget
+    int64_t n_chunks = 0;
+    std::vector<hipEvent_t> ev;         // pool
+    size_t ev_used = 0;                 // [0, 1]: layers kernel; then three per chunk
+};
+
+constexpr int64_t kSoDefaultBudget = 8LL << 30;
+
+namespace smrt_launch {
+void successive_order_release(smrt_dort_ctx* ctx) {
+    SuccessiveOrderState* st = ctx->successive_order;
+    if (!st) return;
+    DevBuf* bufs[] = {&st->nl, &st->thick, &st->fv, &st->temp, &st->p1, &st->p2, &st->freq, &st->theta, &st->lw, &st->kind, &st->sub1,
+                      &st->sub2, &st->subT, &st->gl, &st->pairmap, &st->stage, &st->nsub, &st->nstream, &st->vec, &st->srcterm,
+                      &st->wsoff, &st->chunk, &st->out, &st->status, &st->layer, &st->streams, &st->maxrad, &st->orders};
+    for (DevBuf* b : bufs) b->release();
+    for (hipEvent_t e : st->ev) if (e) (void)hipEventDestroy(e);
+    delete st;
+    ctx->successive_order = nullptr;
+}
+}  // namespace smrt_launch
+
+static const char* so_validate(const smrt_batch* b, int32_t n_iter, double rtol) {
+    if (!b) return "null batch";
+    if (b->n_snowpacks <= 0 || b->n_frequencies <= 0 || b->n_layers_max <= 0) return "empty batch";
+    if (b->n_theta <= 0) return "n_theta must be positive";
+    if (b->mode != SMRT_MODE_PASSIVE) return "the successive_order solver needs a passive sensor";
+    if (n_iter < 1) return "n_iteration_max must be at least 1";
+    if (!(rtol >= 0.0)) return "relative_tolerance must be non-negative";
+    if (b->n_max_stream < 2 || b->n_max_stream > kSoMaxStream) return "the successive_order solver takes 2 to 64 streams";
+    if (b->m_max < 0) return "m_max must be non-negative";
+    if (b->emmodel < SMRT_EM_IBA || b->emmodel > SMRT_EM_RAYLEIGH_HOST) return "unknown emmodel";
+    if (b->microstructure < SMRT_MS_EXPONENTIAL || b->microstructure > SMRT_MS_TEUBNER_STREY) return "unknown microstructure";
+    if (!b->n_layers || !b->thickness || !b->frac_volume || !b->temperature || !b->micro_p1 || !b->frequency || !b->theta)
+        return "null input array";
+    if ((b->microstructure == SMRT_MS_STICKY_HARD_SPHERES || b->layer_kind) && !b->micro_p2) return "stickiness array missing";
+    const char* host = "the successive_order solver has no route for emmodels evaluated on the host";
+    if (!b->layer_kind) {
+        if (b->emmodel == SMRT_EM_HOST || b->emmodel == SMRT_EM_IBA_HOST || b->emmodel == SMRT_EM_RAYLEIGH_HOST) return host;
+        if ((b->emmodel == SMRT_EM_DMRT_QCA_SHORTRANGE || b->emmodel == SMRT_EM_DMRT_QCACP_SHORTRANGE) &&
+            b->microstructure != SMRT_MS_STICKY_HARD_SPHERES)
+            return "the dmrt short-range emmodels are only compatible with sticky_hard_spheres";
+    }
+    for (int s = 0; s < b->n_snowpacks; ++s) {
+        if (b->n_layers[s] < 1 || b->n_layers[s] > b->n_layers_max) return "n_layers out of range";
+        for (int l = 0; b->layer_kind && l < b->n_layers[s]; ++l) {
+            const int k = b->layer_kind[(long long)s * b->n_layers_max + l], em = k & 15, ms = k >> 4;
+            if (em < SMRT_EM_IBA || em > SMRT_EM_RAYLEIGH_HOST || ms < SMRT_MS_EXPONENTIAL || ms > SMRT_MS_TEUBNER_STREY)
+                return "invalid layer_kind entry";
+            if (em == SMRT_EM_HOST || em == SMRT_EM_IBA_HOST || em == SMRT_EM_RAYLEIGH_HOST) return host;
+            if ((em == SMRT_EM_DMRT_QCA_SHORTRANGE || em == SMRT_EM_DMRT_QCACP_SHORTRANGE) && ms != SMRT_MS_STICKY_HARD_SPHERES)
+                return "the dmrt short-range emmodels are only compatible with sticky_hard_spheres";
+        }
+    }
+    if (b->substrate_kind < SMRT_SUBSTRATE_NONE || b->substrate_kind > SMRT_SUBSTRATE_REFLECTOR)
+        return "the successive_order solver takes no substrate, a flat one or a reflector";
+    if (b->substrate_kind != SMRT_SUBSTRATE_NONE && (!b->substrate_p1 || !b->substrate_p2)) return "substrate arrays missing";
+    if (b->host_interface_slot) return "the successive_order solver takes flat interfaces only";
+    if (b->atm_tb_down || b->atm_tb_up || b->atm_transmittance) return "the successive_order solver can not handle atmosphere yet.";
+    if (b->process_coherent_layers) return "the successive_order solver does not process coherent layers";
+    return nullptr;
+}
+
+static int so_upload(smrt_dort_ctx* ctx, DevBuf& buf, const void* src, size_t bytes, size_t* total) {
+    HIPCHK(buf.reserve(bytes));
+    HIPCHK(hipMemcpyAsync(buf.p, src, bytes, hipMemcpyHostToDevice, ctx->stream));
+    *total += bytes;
+    return 0;
+}
+
+static int so_event(smrt_dort_ctx* ctx, SuccessiveOrderState* st) {
+    if (st->ev_used == st->ev.size()) {
+        hipEvent_t e = nullptr;
+        HIPCHK(hipEventCreate(&e));
+        st->ev.push_back(e);
+    }
+    HIPCHK(hipEventRecord(st->ev[st->ev_used++], ctx->stream));
+    return 0;
+}
+
+extern "C" {
+
+int32_t smrt_successive_order_out_stride(const smrt_batch* b, int32_t n_iteration_max) {
+    return (b && n_iteration_max >= 1) ? (n_iteration_max + 1) * 2 * b->n_theta : -1;
+}
+
+int32_t smrt_successive_order_upload_pairs(smrt_dort_ctx* ctx, const smrt_batch* b, int32_t n_iteration_max,
+                                           double relative_tolerance, int64_t workspace_budget_bytes, const int64_t* pairs,
+                                           int64_t n_pairs) {
+    if (!ctx) return -1;
+    const char* why = so_validate(b, n_iteration_max, relative_tolerance);
+    if (why) { ctx->err = why; return -1; }
+    const int64_t all = (int64_t)b->n_snowpacks * b->n_frequencies;
+    if (!pairs) n_pairs = all;
+    else {
+        if (n_pairs <= 0) { ctx->err = "empty pair list"; return -1; }
+        for (int64_t i = 0; i < n_pairs; ++i)
+            if (pairs[i] < 0 || pairs[i] >= all) { ctx->err = "pair index out of bounds"; return -1; }
+    }
+    HIPCHK(hipSetDevice(ctx->device));
+    if (!ctx->successive_order) ctx->successive_order = new SuccessiveOrderState();
+    SuccessiveOrderState* st = ctx->successive_order;
+    st->uploaded = st->launched = false;
+    st->budget = workspace_budget_bytes > 0 ? workspace_budget_bytes : kSoDefaultBudget;
+    const size_t S = b->n_snowpacks, L = b->n_layers_max, F = b->n_frequencies, T = b->n_theta, N = (size_t)n_pairs;
+    const size_t SL = S * L * sizeof(double), FS = F * S, NM = b->n_max_stream, NO = n_iteration_max;
+    // everything but the chunk buffer, counted before anything is reserved: the budget is checked first
+    const size_t Dh = 2 * NM;
+    const size_t out_bytes[] = {(size_t)SO_ROWS * L * N * 8, N * L * 4, N * L * 4, N * L * SO_VECS * Dh * 8, N * L * 8, N * 8,
+                                N * (NO + 1) * 2 * T * 8, N * 4, N * L * 5 * 8, N * (1 + NM) * 8, N * NO * 8, N * 4};
+    size_t fixed = S * 4 + 5 * SL + (b->liquid_water ? SL : 0) + (b->layer_kind ? S * L * 4 : 0) + F * 8 + T * 8 + NM * 8 +
+                   (b->substrate_kind != SMRT_SUBSTRATE_NONE ? 2 * FS * 8 + S * 8 : 0) + (pairs ? N * 8 : 0);
+    for (size_t v : out_bytes) fixed += v;
+    if ((int64_t)fixed >= st->budget) {
+        ctx->err = "the workspace budget of the successive_order solver is smaller than the buffers of the batch itself (" +
+                   std::to_string(fixed) + " bytes)";
+        return -1;
+    }
+    SoBatch d{};
+    d.S = (int)S; d.Lmax = (int)L; d.F = (int)F; d.n_theta = (int)T;
+    d.emmodel = b->emmodel; d.micro = b->microstructure; d.sub_kind = b->substrate_kind; d.nmax = (int)NM;
+    d.n_iter = n_iteration_max; d.rj = b->rayleigh_jeans ? 1 : 0; d.nsamp = azimuth_samples(b->m_max);
+    d.rtol = relative_tolerance;
+    d.n_pairs = n_pairs;
+    size_t up = 0;
+#define SO_UP(buf, src, bytes, field) do { if (so_upload(ctx, st->buf, src, bytes, &up)) return -1; d.field = (decltype(d.field))st->buf.p; } while (0)
+    SO_UP(nl, b->n_layers, S * sizeof(int32_t), n_layers);
+    SO_UP(thick, b->thickness, SL, thickness);
+    SO_UP(fv, b->frac_volume, SL, frac_volume);
+    SO_UP(temp, b->temperature, SL, temperature);
+    SO_UP(p1, b->micro_p1, SL, p1);
+    if (b->micro_p2) SO_UP(p2, b->micro_p2, SL, p2);
+    SO_UP(freq, b->frequency, F * sizeof(double), frequency);
+    SO_UP(theta, b->theta, T * sizeof(double), theta);
+    if (b->liquid_water) SO_UP(lw, b->liquid_water, SL, liquid_water);
+    if (b->layer_kind) SO_UP(kind, b->layer_kind, S * L * sizeof(int32_t), layer_kind);
+    std::vector<double> subT(S, 0.0);
+    if (b->substrate_kind != SMRT_SUBSTRATE_NONE) {
+        SO_UP(sub1, b->substrate_p1, FS * sizeof(double), sub_p1);
+        SO_UP(sub2, b->substrate_p2, FS * sizeof(double), sub_p2);
+        for (size_t s = 0; s < S && b->substrate_temperature; ++s) subT[s] = b->substrate_temperature[s];
+        SO_UP(subT, subT.data(), S * sizeof(double), sub_T);
+    }
+    std::vector<double> gl(NM);
+    smrt_host::gauss_legendre_positive((int)NM, gl.data(), nullptr);
+    SO_UP(gl, gl.data(), NM * sizeof(double), gl_mu);
+    if (pairs) SO_UP(pairmap, pairs, N * sizeof(int64_t), pair_map);
+#undef SO_UP
+    DevBuf* outs[] = {&st->stage, &st->nsub, &st->nstream, &st->vec, &st->srcterm, &st->wsoff, &st->out, &st->status, &st->layer,
+                      &st->streams, &st->maxrad, &st->orders};
+    for (size_t k = 0; k < sizeof(outs) / sizeof(outs[0]); ++k) HIPCHK(outs[k]->reserve(out_bytes[k]));
+    d.stage = (double*)st->stage.p; d.nsub = (int*)st->nsub.p; d.nstream = (int*)st->nstream.p; d.vec = (double*)st->vec.p;
+    d.srcterm = (double*)st->srcterm.p; d.ws_off = (const long long*)st->wsoff.p; d.out = (double*)st->out.p;
+    d.status = (int*)st->status.p; d.layer_out = (double*)st->layer.p; d.streams = (double*)st->streams.p;
+    d.maxrad = (double*)st->maxrad.p; d.orders = (int*)st->orders.p;
+    // the copies above read the caller's (pageable) arrays and this function's own vectors: wait for them
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    st->fixed_bytes = fixed;
+    st->dev = d;
+    st->uploaded = true;
+    return 0;
+}
+
+int32_t smrt_successive_order_launch(smrt_dort_ctx* ctx) {
+    if (!ctx) return -1;
+    SuccessiveOrderState* st = ctx->successive_order;
+    if (!st || !st->uploaded) { ctx->err = "no successive-order batch uploaded"; return -1; }
+    HIPCHK(hipSetDevice(ctx->device));
+    SoBatch d = st->dev;
+    const long long N = d.n_pairs, L = d.Lmax;
+    st->launched = false;
+    st->ev_used = 0;
+    st->deep.clear();
+    // (a) layer scalars and sublayer counts; the counts come back: they size the workspace
+    if (so_event(ctx, st)) return -1;
+    hipLaunchKernelGGL(successive_order_layers_kernel, dim3((unsigned)((N * L + kSoThreads - 1) / kSoThreads)), dim3(kSoThreads), 0,
+                       ctx->stream, d);
+    HIPCHK(hipGetLastError());
+    if (so_event(ctx, st)) return -1;
+    st->nsub_host.resize((size_t)(N * L));
+    HIPCHK(hipMemcpyAsync(st->nsub_host.data(), d.nsub, (size_t)(N * L) * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    // the chunk plan: consecutive rows whose Wt matrices and workspaces fit what the budget leaves
+    const long long Dp = so_dp(d.nmax), Dh = 2 * d.nmax;
+    const long long wt_pair = L * Dp * Dp;                       // doubles
+    const long long avail = (st->budget - (int64_t)st->fixed_bytes) / 8;   // doubles
+    std::vector<long long> ws_off((size_t)N, 0), begin, count, ws_total;
+    long long cur_ws = 0, cur_n = 0, cur_begin = 0, largest = 0;
+    auto close = [&](long long next_begin) {
+        if (cur_n > 0) {
+            begin.push_back(cur_begin); count.push_back(cur_n); ws_total.push_back(cur_ws);
+            if (cur_n * wt_pair + cur_ws > largest) largest = cur_n * wt_pair + cur_ws;
+        }
+        cur_begin = next_begin; cur_n = 0; cur_ws = 0;
+    };
+    for (long long i = 0; i < N; ++i) {
+        long long n_sub = 0, n_lay = 0;
+        for (long long l = 0; l < L; ++l) { const int k = st->nsub_host[(size_t)(i * L + l)]; n_sub += k; n_lay += k > 0; }
+        const long long ws = (2 * n_sub + n_lay) * Dp + 2 * n_lay * Dh;
+        if (wt_pair + ws > avail) { close(i + 1); st->deep.push_back(i); continue; }
+        if ((cur_n + 1) * wt_pair + cur_ws + ws > avail) close(i);
+        ws_off[(size_t)i] = cur_ws;
+        cur_ws += ws; ++cur_n;
+    }
+    close(N);
+    st->n_chunks = (int64_t)begin.size();
+    st->chunk_bytes = (size_t)largest * 8;
+    if (largest > 0) HIPCHK(st->chunk.reserve((size_t)largest * 8));
+    HIPCHK(hipMemcpyAsync(st->wsoff.p, ws_off.data(), (size_t)N * sizeof(long long), hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(hipStreamSynchronize(ctx->stream));   // (ws_off is a local vector)
+    const size_t lds = (size_t)so_lds_doubles(d.nmax, d.n_theta) * sizeof(double);
+    for (size_t c = 0; c < begin.size(); ++c) {
+        d.chunk_begin = begin[c]; d.chunk_count = count[c];
+        d.wt = (double*)st->chunk.p;
+        d.ws = d.wt + count[c] * wt_pair;
+        if (so_event(ctx, st)) return -1;
+        hipLaunchKernelGGL(successive_order_prep_kernel, dim3((unsigned)(count[c] * L)), dim3(kSoThreads), 0, ctx->stream, d);
+        HIPCHK(hipGetLastError());
+        if (so_event(ctx, st)) return -1;
+        hipLaunchKernelGGL(successive_order_sweep_kernel, dim3((unsigned)count[c]), dim3(kSoThreads), lds, ctx->stream, d);
+        HIPCHK(hipGetLastError());
+        if (so_event(ctx, st)) return -1;
+    }
+    st->launched = true;
+    return 0;
+}
+
+int32_t smrt_successive_order_sync(smrt_dort_ctx* ctx) {
+    if (!ctx) return -1;
+    HIPCHK(hipSetDevice(ctx->device));
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    return 0;
+}
+
+int32_t smrt_successive_order_kernel_ms(smrt_dort_ctx* ctx, double* ms2) {
+    if (!ctx || !ms2) return -1;
+    SuccessiveOrderState* st = ctx->successive_order;
+    if (!st || !st->launched) { ctx->err = "no successive-order launch to time"; return -1; }
+    HIPCHK(hipSetDevice(ctx->device));
+    HIPCHK(hipEventSynchronize(st->ev[st->ev_used - 1]));
+    float a = 0.f;
+    HIPCHK(hipEventElapsedTime(&a, st->ev[0], st->ev[1]));
+    double prep = a, sweep = 0.0;
+    for (size_t k = 2; k + 2 < st->ev_used; k += 3) {
+        HIPCHK(hipEventElapsedTime(&a, st->ev[k], st->ev[k + 1]));
+        prep += a;
+        HIPCHK(hipEventElapsedTime(&a, st->ev[k + 1], st->ev[k + 2]));
+        sweep += a;
+    }
+    ms2[0] = prep; ms2[1] = sweep;
+    return 0;
+}
+
+int32_t smrt_successive_order_launch_info(smrt_dort_ctx* ctx, int64_t* info, int32_t capacity) {
+    if (!ctx) return -1;
+    SuccessiveOrderState* st = ctx->successive_order;
+    if (!st || !st->launched) { ctx->err = "no successive-order launch to describe"; return -1; }
+    const int64_t v[] = {st->n_chunks, (int64_t)(st->fixed_bytes + st->chunk_bytes), (int64_t)st->deep.size(), st->budget};
+    const int32_t n = (int32_t)(sizeof(v) / sizeof(v[0]));
+    for (int32_t i = 0; info && i < n && i < capacity; ++i) info[i] = v[i];
+    return n;
+}
+
+int32_t smrt_successive_order_download(smrt_dort_ctx* ctx, double* out, int32_t* status, double* layer_out, double* streams,
+                                       int32_t* sublayers, double* max_radiance, int32_t* orders) {
+    if (!ctx) return -1;
+    SuccessiveOrderState* st = ctx->successive_order;
+    if (!st || !st->launched) { ctx->err = "no successive-order launch to download"; return -1; }
+    HIPCHK(hipSetDevice(ctx->device));
+    const SoBatch& d = st->dev;
+    const size_t N = (size_t)d.n_pairs, L = d.Lmax, row = (size_t)(d.n_iter + 1) * 2 * d.n_theta, NO = d.n_iter, NS = 1 + d.nmax;
+    if (out) HIPCHK(hipMemcpyAsync(out, d.out, N * row * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    if (status) HIPCHK(hipMemcpyAsync(status, d.status, N * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
+    if (layer_out) HIPCHK(hipMemcpyAsync(layer_out, d.layer_out, N * L * 5 * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    if (streams) HIPCHK(hipMemcpyAsync(streams, d.streams, N * NS * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    if (max_radiance) HIPCHK(hipMemcpyAsync(max_radiance, d.maxrad, N * NO * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    if (orders) HIPCHK(hipMemcpyAsync(orders, d.orders, N * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    if (sublayers) std::memcpy(sublayers, st->nsub_host.data(), N * L * sizeof(int32_t));
+    for (long long i : st->deep) {   // the rows no kernel touched
+        if (out) for (size_t k = 0; k < row; ++k) out[(size_t)i * row + k] = NAN;
+        if (status) status[i] = ST_DEPTH;
+        if (streams) for (size_t k = 0; k < NS; ++k) streams[(size_t)i * NS + k] = 0.0;
+        if (max_radiance) for (size_t k = 0; k < NO; ++k) max_radiance[(size_t)i * NO + k] = NAN;
+        if (orders) orders[i] = 0;
+    }
+    return 0;
+}
+
+int32_t smrt_successive_order_run_pairs(smrt_dort_ctx* ctx, const smrt_batch* batch, int32_t n_iteration_max,
+                                        double relative_tolerance, int64_t workspace_budget_bytes, const int64_t* pairs,
+                                        int64_t n_pairs, double* out, int32_t* status, double* layer_out, double* streams,
+                                        int32_t* sublayers, double* max_radiance, int32_t* orders) {
+    if (smrt_successive_order_upload_pairs(ctx, batch, n_iteration_max, relative_tolerance, workspace_budget_bytes, pairs, n_pairs))
+        return -1;
+    if (smrt_successive_order_launch(ctx)) return -1;
+    return smrt_successive_order_download(ctx, out, status, layer_out, streams, sublayers, max_radiance, orders);
+}
+
+}  // extern "C"
