@@ -551,6 +551,46 @@ int32_t smrt_successive_order_kernel_ms(smrt_dort_ctx* ctx, double* ms2);
  * budget.  Returns the number of entries; at most `capacity` are written. */
 int32_t smrt_successive_order_launch_info(smrt_dort_ctx* ctx, int64_t* info, int32_t capacity);
 
+/*
+ * The multi-Fresnel thermal emission solver (the reference's smrt/rtsolver/multifresnel_thermalemission.py and
+ * multifresnel/multifresnel.py: Hebert et al. 2015; annex of Zeiger et al. 2024) on the same context.  Passive sensors only,
+ * Flat interfaces, no substrate or a Flat one, no atmosphere, emmodels with a device implementation: only their effective
+ * permittivity enters the solution (ks and ka are reported).  The batch is the smrt_batch of DORT: layers, kinds, wet snow,
+ * frequencies and the flat substrate with its temperature are read (the substrate becomes one more layer, 1e10 m thick);
+ * theta, n_max_stream, m_max, phase_normalization, rayleigh_jeans and prune_optical_depth are ignored; an atmosphere, host_*
+ * arrays and process_coherent_layers are refused.  What the solver needs beyond the batch are arguments:
+ *   mu                   [n_theta] the cosines of the sensor's angles, in the air; 0 <= mu <= 1
+ *   prune_deep_snowpack  the optical depth every angle starts with: the optical depth of a layer is clipped, per angle, to what
+ *                        that angle has left; the chain of a pair stops after the first layer at which the remainder of the
+ *                        steepest angle (largest mu) is negative;
+ *   prune_none           non-zero: no pruning (the reference's None), prune_deep_snowpack is not read.
+ * Per pair and angle the solution is the product, left to right, of one 2 x 3 affine matrix per layer; there is no Planck
+ * function: the temperatures are the physical ones.
+ * Outputs, one row per pair: out [n_theta][2] kelvin (V, H); status [n_theta] SMRT_OK, SMRT_ERR_INPUT (an invalid layer: every
+ * angle of the pair) or SMRT_ERR_NONFINITE (this angle: a reflectivity of 1 divides by zero) -- the element is NaN then;
+ * optional (may be NULL) layers_used [1] int32 (layer matrices multiplied, the substrate counts), tau_snowpack [1] (the steepest
+ * angle's clipped optical depths summed over those layers), layer_out [n_layers_max][5] as DORT's (column 4 is zero).
+ */
+#define SMRT_ERR_NONFINITE 8
+/* Doubles per pair of `out`: 2 x n_theta. */
+int32_t smrt_multifresnel_out_stride(const smrt_batch* b);
+/* One shot over the listed pairs (semantics of smrt_dort_run_pairs; pairs == NULL: every pair of the batch in order,
+ * n_pairs ignored).  Returns 0, negative on error. */
+int32_t smrt_multifresnel_run_pairs(smrt_dort_ctx* ctx, const smrt_batch* batch, const double* mu, double prune_deep_snowpack,
+                                    int32_t prune_none, const int64_t* pairs, int64_t n_pairs, double* out, int32_t* status,
+                                    int32_t* layers_used, double* tau_snowpack, double* layer_out);
+/* Split form: upload once, launch (asynchronous on the context's stream) any number of times, sync, download.  The upload
+ * returns when the copies are done.  One host thread per context, as for DORT. */
+int32_t smrt_multifresnel_upload_pairs(smrt_dort_ctx* ctx, const smrt_batch* batch, const double* mu, double prune_deep_snowpack,
+                                       int32_t prune_none, const int64_t* pairs, int64_t n_pairs);
+int32_t smrt_multifresnel_launch(smrt_dort_ctx* ctx);
+int32_t smrt_multifresnel_sync(smrt_dort_ctx* ctx);
+int32_t smrt_multifresnel_download(smrt_dort_ctx* ctx, double* out, int32_t* status, int32_t* layers_used, double* tau_snowpack,
+                                   double* layer_out);
+/* HIP-event time (ms) of the two kernels of the last launch, after a sync: ms2[0] the per-(pair, layer) kernel, ms2[1] the
+ * per-(pair, angle) kernel.  Returns 0, negative on error. */
+int32_t smrt_multifresnel_kernel_ms(smrt_dort_ctx* ctx, double* ms2);
+
 #if defined(__GNUC__)
 #pragma GCC visibility pop
 #endif

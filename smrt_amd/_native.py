@@ -37,6 +37,8 @@ STATUS_MESSAGES = {
        "emmodel evaluated on the host -- a negative ka / permittivity or a stream count that differs from the device's).",
     6: "process_coherent_layers: the last layer is coherent, or two successive layers are coherent; this is not supported.",
     7: "snowpack optically too deep for the successive_order workspace: N sublayers",
+    8: "The multi-Fresnel chain gave a non-finite brightness temperature (a reflectivity of 1, e.g. at a grazing angle, divides "
+       "by zero).",
 }
 
 
@@ -313,6 +315,26 @@ class SuccessiveOrderOutput:
                 _dptr(self.max_radiance), i32(self.orders))
 
 
+class MultiFresnelOutput:
+    """Outputs of the multi-Fresnel thermal emission solver for `pair_count` pairs: values [n_theta][2] kelvin (V, H), status
+    [n_theta] (one word per element), layers_used, tau_snowpack, layers [Lmax][5] as DORT's; streams [1 + n_theta] holds the
+    sensor cosines the way DORT's output holds its air streams (Result.other_data)."""
+
+    def __init__(self, batch, pair_count, mu):
+        Lmax, nt = int(batch.struct.n_layers_max), int(batch.struct.n_theta)
+        self.values = np.empty((pair_count, nt, 2))
+        self.status = np.empty((pair_count, nt), dtype=np.int32)
+        self.layers_used = np.empty(pair_count, dtype=np.int32)
+        self.tau_snowpack = np.empty(pair_count)
+        self.layers = np.empty((pair_count, Lmax, 5))
+        order = np.sort(np.asarray(mu, float))[::-1]
+        self.streams = np.broadcast_to(np.concatenate([[float(nt)], order]), (pair_count, 1 + nt))
+
+    def pointers(self):
+        i32 = lambda a: a.ctypes.data_as(C.POINTER(C.c_int32))  # noqa: E731
+        return (_dptr(self.values), i32(self.status), i32(self.layers_used), _dptr(self.tau_snowpack), _dptr(self.layers))
+
+
 _lib = None
 
 
@@ -439,6 +461,22 @@ def load_library():
     lib.smrt_successive_order_kernel_ms.restype = C.c_int32
     lib.smrt_successive_order_launch_info.argtypes = [C.c_void_p, P(C.c_int64), C.c_int32]
     lib.smrt_successive_order_launch_info.restype = C.c_int32
+    mf_out = [P(C.c_double), P(C.c_int32), P(C.c_int32), P(C.c_double), P(C.c_double)]
+    mf_in = [C.c_void_p, P(SmrtBatch), P(C.c_double), C.c_double, C.c_int32, P(C.c_int64), C.c_int64]
+    lib.smrt_multifresnel_out_stride.argtypes = [P(SmrtBatch)]
+    lib.smrt_multifresnel_out_stride.restype = C.c_int32
+    lib.smrt_multifresnel_run_pairs.argtypes = mf_in + mf_out
+    lib.smrt_multifresnel_run_pairs.restype = C.c_int32
+    lib.smrt_multifresnel_upload_pairs.argtypes = mf_in
+    lib.smrt_multifresnel_upload_pairs.restype = C.c_int32
+    lib.smrt_multifresnel_launch.argtypes = [C.c_void_p]
+    lib.smrt_multifresnel_launch.restype = C.c_int32
+    lib.smrt_multifresnel_sync.argtypes = [C.c_void_p]
+    lib.smrt_multifresnel_sync.restype = C.c_int32
+    lib.smrt_multifresnel_download.argtypes = [C.c_void_p] + mf_out
+    lib.smrt_multifresnel_download.restype = C.c_int32
+    lib.smrt_multifresnel_kernel_ms.argtypes = [C.c_void_p, P(C.c_double)]
+    lib.smrt_multifresnel_kernel_ms.restype = C.c_int32
     check_struct_layout(lib)
     _lib = lib
     return lib
@@ -491,6 +529,8 @@ EXPORTED_SYMBOLS = [
     "smrt_successive_order_out_stride", "smrt_successive_order_run_pairs", "smrt_successive_order_upload_pairs",
     "smrt_successive_order_launch", "smrt_successive_order_sync", "smrt_successive_order_download",
     "smrt_successive_order_kernel_ms", "smrt_successive_order_launch_info",
+    "smrt_multifresnel_out_stride", "smrt_multifresnel_run_pairs", "smrt_multifresnel_upload_pairs", "smrt_multifresnel_launch",
+    "smrt_multifresnel_sync", "smrt_multifresnel_download", "smrt_multifresnel_kernel_ms",
 ]
 
 
@@ -716,6 +756,62 @@ class DortContext:
             self._check(int(self._lib.smrt_successive_order_launch_info(self._h, a.ctypes.data_as(C.POINTER(C.c_int64)), 4) < 0),
                         "smrt_successive_order_launch_info")
         return dict(chunks=int(a[0]), reserved_bytes=int(a[1]), over_budget=int(a[2]), budget=int(a[3]))
+
+    # ---- the multi-Fresnel thermal emission solver (smrt_multifresnel_*) -------------------------------------------
+    def _check_negative(self, rc, what):
+        """The convention of include/smrt_dort.h: negative means error (a count or 0 is success)."""
+        if rc < 0:
+            raise SMRTError(f"{what} failed: {self._lib.smrt_dort_last_error(self._h).decode()}")
+
+    @staticmethod
+    def _multifresnel_args(batch, mu, prune_deep_snowpack, pairs):
+        mu = np.ascontiguousarray(np.atleast_1d(mu), dtype=np.float64)
+        if len(mu) != int(batch.struct.n_theta):
+            raise SMRTError("one sensor cosine per angle of the batch is needed")
+        if pairs is not None:
+            pairs = np.ascontiguousarray(pairs, dtype=np.int64)
+        none = prune_deep_snowpack is None
+        return (C.byref(batch.struct), _dptr(mu), 0.0 if none else float(prune_deep_snowpack), 1 if none else 0,
+                pairs.ctypes.data_as(C.POINTER(C.c_int64)) if pairs is not None else None,
+                len(pairs) if pairs is not None else -1), mu, pairs
+
+    def multifresnel_run(self, batch: PackedBatch, mu, prune_deep_snowpack=10, pairs=None) -> MultiFresnelOutput:
+        """One shot (H2D, two kernels, D2H) for every pair of the batch or the listed ones (row i = pairs[i]).  mu: the
+        cosines of the sensor's angles; prune_deep_snowpack: an optical depth, or None for no pruning."""
+        args, mu, pairs = self._multifresnel_args(batch, mu, prune_deep_snowpack, pairs)
+        o = MultiFresnelOutput(batch, batch.n_pairs if pairs is None else len(pairs), mu)
+        with self.lock:
+            self._check_negative(self._lib.smrt_multifresnel_run_pairs(self._h, *args, *o.pointers()), "smrt_multifresnel_run_pairs")
+        return o
+
+    def multifresnel_upload(self, batch: PackedBatch, mu, prune_deep_snowpack=10, pairs=None):
+        """Split form (upload once, launch any number of times, sync, download); see first_order_upload for the lock."""
+        args, mu, pairs = self._multifresnel_args(batch, mu, prune_deep_snowpack, pairs)
+        with self.lock:
+            self._check_negative(self._lib.smrt_multifresnel_upload_pairs(self._h, *args), "smrt_multifresnel_upload_pairs")
+            self._multifresnel_resident = (batch, mu, batch.n_pairs if pairs is None else len(pairs))
+
+    def multifresnel_launch(self):
+        with self.lock:
+            self._check_negative(self._lib.smrt_multifresnel_launch(self._h), "smrt_multifresnel_launch")
+
+    def multifresnel_sync(self):
+        with self.lock:
+            self._check_negative(self._lib.smrt_multifresnel_sync(self._h), "smrt_multifresnel_sync")
+
+    def multifresnel_download(self) -> MultiFresnelOutput:
+        with self.lock:
+            batch, mu, n = self._multifresnel_resident
+            o = MultiFresnelOutput(batch, n, mu)
+            self._check_negative(self._lib.smrt_multifresnel_download(self._h, *o.pointers()), "smrt_multifresnel_download")
+        return o
+
+    def multifresnel_kernel_ms(self):
+        """HIP-event ms of the (pair, layer) kernel and of the (pair, angle) kernel of the last launch."""
+        a = np.zeros(2)
+        with self.lock:
+            self._check_negative(self._lib.smrt_multifresnel_kernel_ms(self._h, _dptr(a)), "smrt_multifresnel_kernel_ms")
+        return float(a[0]), float(a[1])
 
     def ft_even_phase(self, emmodel, microstructure, frequency, frac_volume, temperature, p1, p2, mu_s, mu_i, m_max, npol):
         """Azimuthal modes of the phase matrix of one layer: array [npol, npol, m_max + 1, len(mu_s), len(mu_i)]."""
