@@ -552,6 +552,54 @@ int32_t smrt_successive_order_kernel_ms(smrt_dort_ctx* ctx, double* ms2);
 int32_t smrt_successive_order_launch_info(smrt_dort_ctx* ctx, int64_t* info, int32_t capacity);
 
 /*
+ * The successive-order BACKSCATTER solver: the same method in active mode (the active branches of the reference's
+ * smrt/rtsolver/successive_order.py), backscatter order by order on DORT's discrete ordinates with three polarisations (V, H,
+ * U).  The batch is the smrt_batch of DORT with mode SMRT_MODE_ACTIVE: layers, kinds, wet snow, frequencies, n_max_stream (2
+ * to 64), phi and the flat substrate (reflection only) are read; its theta, n_theta and m_max are NOT: the incidence angles
+ * and the number of azimuth modes are arguments.  A reflector substrate (no third Stokes component), host_* arrays,
+ * process_coherent_layers and layer kinds evaluated by the caller are refused.
+ *   n_iteration_max, relative_tolerance  as above; the tolerance is relative_tolerance x the largest emerging radiance of
+ *                       mode 0 at order 0 and stops every mode pass by itself; the coherent pass runs every order;
+ *   n_theta_inc, theta_inc  the incidence angles (rad); the incident streams are the air streams that bracket them;
+ *   incident_npol       1 (V), 2 (V, H) or 3 (V, H, U) incident polarisations: columns = incident_npol x incident streams;
+ *   m_max               azimuth modes 0 .. m_max (at most 2 for the Rayleigh-family emmodels);
+ *   workspace_budget_bytes  as above; per pair the chunk buffer holds (m_max + 1) x n_layers_max x (16-padded 6
+ *                       n_max_stream)^2 doubles of weighted phase matrices and (m_max + 2) passes x columns x ((2 K + L) x
+ *                       padded directions + (2 L + 1) x 3 n_max_stream) doubles of workspace, K its sublayers, columns =
+ *                       incident_npol x min(2 n_theta_inc, n_max_stream).
+ * Outputs, one row per pair: out [3][3][n_theta_inc][n_iteration_max + 1] (scattered polarisation, incident polarisation,
+ * angle, order; the last entry is the total) as DORT's active output; status SMRT_OK, SMRT_ERR_INPUT or SMRT_ERR_DEPTH (the
+ * row is NaN then); optional (may be NULL) layer_out, streams, sublayers as above, max_radiance [m_max + 2][n_iteration_max]
+ * (per pass -- the coherent pass first, then the modes -- the largest emerging radiance of every order run, NaN after the
+ * stop), orders [m_max + 2] int32 (orders run per pass).
+ * The prefix is smrt_so_active_, not smrt_successive_order_active_: the set of functions whose names begin with
+ * smrt_successive_order_ is the passive solver's eight and is counted by the suite.
+ */
+/* Doubles per pair of `out`: 9 x n_theta_inc x (n_iteration_max + 1). */
+int32_t smrt_so_active_out_stride(int32_t n_theta_inc, int32_t n_iteration_max);
+int32_t smrt_so_active_run_pairs(smrt_dort_ctx* ctx, const smrt_batch* batch, int32_t n_iteration_max,
+                                               double relative_tolerance, int32_t n_theta_inc, const double* theta_inc,
+                                               int32_t incident_npol, int32_t m_max, int64_t workspace_budget_bytes,
+                                               const int64_t* pairs, int64_t n_pairs, double* out, int32_t* status, double* layer_out,
+                                               double* streams, int32_t* sublayers, double* max_radiance, int32_t* orders);
+int32_t smrt_so_active_upload_pairs(smrt_dort_ctx* ctx, const smrt_batch* batch, int32_t n_iteration_max,
+                                                  double relative_tolerance, int32_t n_theta_inc, const double* theta_inc,
+                                                  int32_t incident_npol, int32_t m_max, int64_t workspace_budget_bytes,
+                                                  const int64_t* pairs, int64_t n_pairs);
+/* As smrt_successive_order_launch, the launch is only partly asynchronous: it waits for the sublayer counts of its first
+ * kernel, plans the chunks on the host from them -- again on every launch of the same upload -- and waits for the upload of
+ * the workspace offsets; from there on the chunk kernels are queued without waiting. */
+int32_t smrt_so_active_launch(smrt_dort_ctx* ctx);
+int32_t smrt_so_active_sync(smrt_dort_ctx* ctx);
+int32_t smrt_so_active_download(smrt_dort_ctx* ctx, double* out, int32_t* status, double* layer_out, double* streams,
+                                              int32_t* sublayers, double* max_radiance, int32_t* orders);
+/* HIP-event time (ms) of the last launch, after a sync: ms3[0] the preparation kernels, ms3[1] the sweep kernel, ms3[2] the
+ * combine kernel, each summed over the chunks. */
+int32_t smrt_so_active_kernel_ms(smrt_dort_ctx* ctx, double* ms3);
+/* As smrt_successive_order_launch_info: returns the number of entries (>= 0), negative on error. */
+int32_t smrt_so_active_launch_info(smrt_dort_ctx* ctx, int64_t* info, int32_t capacity);
+
+/*
  * The multi-Fresnel thermal emission solver (the reference's smrt/rtsolver/multifresnel_thermalemission.py and
  * multifresnel/multifresnel.py: Hebert et al. 2015; annex of Zeiger et al. 2024) on the same context.  Passive sensors only,
  * Flat interfaces, no substrate or a Flat one, no atmosphere, emmodels with a device implementation: only their effective

@@ -315,6 +315,29 @@ class SuccessiveOrderOutput:
                 _dptr(self.max_radiance), i32(self.orders))
 
 
+class SuccessiveOrderActiveOutput:
+    """Outputs of the successive-order backscatter solver for `pair_count` pairs: values [3][3][n_theta_inc][n_iteration_max
+    + 1] (scattered polarisation, incident polarisation, angle, order; the last entry of the order axis is the total), status,
+    layers [Lmax][5] and streams [1 + n_max_stream] as DORT's, sublayers [Lmax], max_radiance [m_max + 2][n_iteration_max] (per
+    pass -- coherent, then the modes -- the largest emerging radiance of every order run, NaN after the stop), orders [m_max +
+    2] (orders run per pass)."""
+
+    def __init__(self, batch, pair_count, n_iteration_max, n_theta_inc, m_max):
+        Lmax, nmax = int(batch.struct.n_layers_max), int(batch.struct.n_max_stream)
+        self.values = np.empty((pair_count, 3, 3, n_theta_inc, n_iteration_max + 1))
+        self.status = np.empty(pair_count, dtype=np.int32)
+        self.layers = np.empty((pair_count, Lmax, 5))
+        self.streams = np.empty((pair_count, 1 + nmax))
+        self.sublayers = np.empty((pair_count, Lmax), dtype=np.int32)
+        self.max_radiance = np.empty((pair_count, m_max + 2, n_iteration_max))
+        self.orders = np.empty((pair_count, m_max + 2), dtype=np.int32)
+
+    def pointers(self):
+        i32 = lambda a: a.ctypes.data_as(C.POINTER(C.c_int32))  # noqa: E731
+        return (_dptr(self.values), i32(self.status), _dptr(self.layers), _dptr(self.streams), i32(self.sublayers),
+                _dptr(self.max_radiance), i32(self.orders))
+
+
 class MultiFresnelOutput:
     """Outputs of the multi-Fresnel thermal emission solver for `pair_count` pairs: values [n_theta][2] kelvin (V, H), status
     [n_theta] (one word per element), layers_used, tau_snowpack, layers [Lmax][5] as DORT's; streams [1 + n_theta] holds the
@@ -461,6 +484,24 @@ def load_library():
     lib.smrt_successive_order_kernel_ms.restype = C.c_int32
     lib.smrt_successive_order_launch_info.argtypes = [C.c_void_p, P(C.c_int64), C.c_int32]
     lib.smrt_successive_order_launch_info.restype = C.c_int32
+    soa_in = [C.c_void_p, P(SmrtBatch), C.c_int32, C.c_double, C.c_int32, P(C.c_double), C.c_int32, C.c_int32, C.c_int64, P(C.c_int64),
+              C.c_int64]
+    lib.smrt_so_active_out_stride.argtypes = [C.c_int32, C.c_int32]
+    lib.smrt_so_active_out_stride.restype = C.c_int32
+    lib.smrt_so_active_run_pairs.argtypes = soa_in + so_out
+    lib.smrt_so_active_run_pairs.restype = C.c_int32
+    lib.smrt_so_active_upload_pairs.argtypes = soa_in
+    lib.smrt_so_active_upload_pairs.restype = C.c_int32
+    lib.smrt_so_active_launch.argtypes = [C.c_void_p]
+    lib.smrt_so_active_launch.restype = C.c_int32
+    lib.smrt_so_active_sync.argtypes = [C.c_void_p]
+    lib.smrt_so_active_sync.restype = C.c_int32
+    lib.smrt_so_active_download.argtypes = [C.c_void_p] + so_out
+    lib.smrt_so_active_download.restype = C.c_int32
+    lib.smrt_so_active_kernel_ms.argtypes = [C.c_void_p, P(C.c_double)]
+    lib.smrt_so_active_kernel_ms.restype = C.c_int32
+    lib.smrt_so_active_launch_info.argtypes = [C.c_void_p, P(C.c_int64), C.c_int32]
+    lib.smrt_so_active_launch_info.restype = C.c_int32
     mf_out = [P(C.c_double), P(C.c_int32), P(C.c_int32), P(C.c_double), P(C.c_double)]
     mf_in = [C.c_void_p, P(SmrtBatch), P(C.c_double), C.c_double, C.c_int32, P(C.c_int64), C.c_int64]
     lib.smrt_multifresnel_out_stride.argtypes = [P(SmrtBatch)]
@@ -529,6 +570,8 @@ EXPORTED_SYMBOLS = [
     "smrt_successive_order_out_stride", "smrt_successive_order_run_pairs", "smrt_successive_order_upload_pairs",
     "smrt_successive_order_launch", "smrt_successive_order_sync", "smrt_successive_order_download",
     "smrt_successive_order_kernel_ms", "smrt_successive_order_launch_info",
+    "smrt_so_active_out_stride", "smrt_so_active_run_pairs", "smrt_so_active_upload_pairs", "smrt_so_active_launch",
+    "smrt_so_active_sync", "smrt_so_active_download", "smrt_so_active_kernel_ms", "smrt_so_active_launch_info",
     "smrt_multifresnel_out_stride", "smrt_multifresnel_run_pairs", "smrt_multifresnel_upload_pairs", "smrt_multifresnel_launch",
     "smrt_multifresnel_sync", "smrt_multifresnel_download", "smrt_multifresnel_kernel_ms",
 ]
@@ -755,6 +798,70 @@ class DortContext:
             # (returns the number of entries it has, -1 on error)
             self._check(int(self._lib.smrt_successive_order_launch_info(self._h, a.ctypes.data_as(C.POINTER(C.c_int64)), 4) < 0),
                         "smrt_successive_order_launch_info")
+        return dict(chunks=int(a[0]), reserved_bytes=int(a[1]), over_budget=int(a[2]), budget=int(a[3]))
+
+    # ---- the successive-order backscatter solver (smrt_so_active_*) -----------------------------------------------
+    @staticmethod
+    def _so_active_args(batch, n_iteration_max, relative_tolerance, theta_inc, incident_npol, m_max, workspace_budget, pairs):
+        if pairs is not None:
+            pairs = np.ascontiguousarray(pairs, dtype=np.int64)
+        theta_inc = np.ascontiguousarray(np.atleast_1d(theta_inc), dtype=np.float64)
+        return (C.byref(batch.struct), int(n_iteration_max), float(relative_tolerance), len(theta_inc), _dptr(theta_inc),
+                int(incident_npol), int(m_max), int(workspace_budget or 0),
+                pairs.ctypes.data_as(C.POINTER(C.c_int64)) if pairs is not None else None,
+                len(pairs) if pairs is not None else -1), pairs, theta_inc
+
+    def so_active_run(self, batch: PackedBatch, theta_inc, n_iteration_max=50, relative_tolerance=0.001, incident_npol=2, m_max=2,
+                      pairs=None, workspace_budget=None) -> SuccessiveOrderActiveOutput:
+        """One shot (H2D, kernels chunk after chunk, D2H) for every pair of the (active) batch or the listed ones (row i =
+        pairs[i]).  theta_inc: incidence angles (rad); workspace_budget: bytes everything reserved on the device stays inside."""
+        args, pairs, theta_inc = self._so_active_args(batch, n_iteration_max, relative_tolerance, theta_inc, incident_npol, m_max,
+                                                      workspace_budget, pairs)
+        o = SuccessiveOrderActiveOutput(batch, batch.n_pairs if pairs is None else len(pairs), int(n_iteration_max), len(theta_inc),
+                                        int(m_max))
+        with self.lock:
+            self._check(self._lib.smrt_so_active_run_pairs(self._h, *args, *o.pointers()), "smrt_so_active_run_pairs")
+        return o
+
+    def so_active_upload(self, batch: PackedBatch, theta_inc, n_iteration_max=50, relative_tolerance=0.001, incident_npol=2, m_max=2,
+                         pairs=None, workspace_budget=None):
+        """Split form (upload once, launch any number of times, sync, download); see first_order_upload for the lock."""
+        args, pairs, theta_inc = self._so_active_args(batch, n_iteration_max, relative_tolerance, theta_inc, incident_npol, m_max,
+                                                      workspace_budget, pairs)
+        with self.lock:
+            self._check(self._lib.smrt_so_active_upload_pairs(self._h, *args), "smrt_so_active_upload_pairs")
+            self._so_active_resident = (batch, pairs, batch.n_pairs if pairs is None else len(pairs), int(n_iteration_max),
+                                        len(theta_inc), int(m_max))
+
+    def so_active_launch(self):
+        with self.lock:
+            self._check(self._lib.smrt_so_active_launch(self._h), "smrt_so_active_launch")
+
+    def so_active_sync(self):
+        with self.lock:
+            self._check(self._lib.smrt_so_active_sync(self._h), "smrt_so_active_sync")
+
+    def so_active_download(self) -> SuccessiveOrderActiveOutput:
+        with self.lock:
+            batch, _, n, n_it, n_theta, m_max = self._so_active_resident
+            o = SuccessiveOrderActiveOutput(batch, n, n_it, n_theta, m_max)
+            self._check(self._lib.smrt_so_active_download(self._h, *o.pointers()), "smrt_so_active_download")
+        return o
+
+    def so_active_kernel_ms(self):
+        """HIP-event ms of the preparation kernels, the sweep kernel and the combine kernel of the last launch."""
+        a = np.zeros(3)
+        with self.lock:
+            self._check(self._lib.smrt_so_active_kernel_ms(self._h, _dptr(a)), "smrt_so_active_kernel_ms")
+        return float(a[0]), float(a[1]), float(a[2])
+
+    def so_active_launch_info(self):
+        """dict(chunks, reserved_bytes, over_budget, budget) of the last launch."""
+        a = np.zeros(4, dtype=np.int64)
+        with self.lock:
+            # (returns the number of entries it has, negative on error)
+            self._check(int(self._lib.smrt_so_active_launch_info(self._h, a.ctypes.data_as(C.POINTER(C.c_int64)), 4) < 0),
+                        "smrt_so_active_launch_info")
         return dict(chunks=int(a[0]), reserved_bytes=int(a[1]), over_budget=int(a[2]), budget=int(a[3]))
 
     # ---- the multi-Fresnel thermal emission solver (smrt_multifresnel_*) -------------------------------------------

@@ -88,6 +88,8 @@ struct smrt_dort_ctx {
     struct FirstOrderState* first_order = nullptr;
     // the successive-order solver (successive_order.hip): likewise
     struct SuccessiveOrderState* successive_order = nullptr;
+    // the successive-order backscatter solver (successive_order_active.hip): likewise
+    struct SuccessiveOrderActiveState* successive_order_active = nullptr;
     // the multi-Fresnel thermal emission solver (multifresnel.hip): likewise
     struct MultiFresnelState* multifresnel = nullptr;
 };
@@ -138,6 +140,8 @@ hipError_t pair_cost(smrt_dort_ctx* ctx, const smrt::DevBatch& d, double* cost_d
 void first_order_release(smrt_dort_ctx* ctx);
 // successive_order.hip: frees ctx->successive_order (smrt_dort_destroy)
 void successive_order_release(smrt_dort_ctx* ctx);
+// successive_order_active.hip: frees ctx->successive_order_active (smrt_dort_destroy)
+void successive_order_active_release(smrt_dort_ctx* ctx);
 // multifresnel.hip: frees ctx->multifresnel (smrt_dort_destroy)
 void multifresnel_release(smrt_dort_ctx* ctx);
 }  // namespace smrt_launch

@@ -138,10 +138,31 @@ class SuccessiveOrder(object):
     def _check_sensor(sensor):
         if sensor.mode != "P":
             raise SMRTError("the successive_order solver of smrt_amd is only suitable for passive microwave: active sensors "
-                            "are not implemented.")
+                            "are not implemented here, use rtsolver 'successive_order_backscatter'.")
         if np.ndim(sensor.frequency) != 0:
             raise SMRTError("the successive_order solver does not broadcast the frequency: split the sensor first "
                             "(Model.run does)")
+
+    # what the active sibling (rtsolver/successive_order_backscatter.py) replaces; the grouping and the pair map are shared
+    _NAME = "successive_order"
+
+    @staticmethod
+    def _sensor_key(sensor):
+        """What must be uniform inside one launch, beyond the substrate kind."""
+        return tuple(np.round(sensor.theta_deg, 12))
+
+    def _context(self):
+        return get_context((self.devices or [None])[0])
+
+    @staticmethod
+    def _solution_class():
+        return _Solution
+
+    def _run(self, ctx, batch, sensor0, pairs):
+        """One launch (under the context lock): its output and its launch_info."""
+        out = ctx.successive_order_run(batch, self.n_iteration_max, self.relative_tolerance, pairs=pairs,
+                                       workspace_budget=self.workspace_budget)
+        return out, ctx.successive_order_launch_info()
 
     def _packer(self):
         return _Packer(n_max_stream=self.n_max_stream, m_max=self.m_max, error_handling=self.error_handling,
@@ -167,12 +188,12 @@ class SuccessiveOrder(object):
         s_code = np.empty(len(sensors), np.int64)
         for k, sensor in enumerate(sensors):
             self._check_sensor(sensor)
-            s_code[k] = sensor_keys.setdefault(tuple(np.round(sensor.theta_deg, 12)), len(sensor_keys))
+            s_code[k] = sensor_keys.setdefault(self._sensor_key(sensor), len(sensor_keys))
         p_code = np.empty(len(packs), np.int64)
         packed = []
         for k, sp in enumerate(packs):
             if not isinstance(emmodel_names, str) and any(not isinstance(e, str) for e in emmodel_names[k]):
-                raise SMRTError("the successive_order solver has no route for emmodels evaluated on the host: use an emmodel "
+                raise SMRTError(f"the {self._NAME} solver has no route for emmodels evaluated on the host: use an emmodel "
                                 "with a device implementation (iba, dmrt_qca_shortrange, dmrt_qcacp_shortrange, nonscattering)")
             packed.append(self._check_snowpack(sp))
             if packed[-1] is not sp and packer._plan_facts is not None:
@@ -180,8 +201,8 @@ class SuccessiveOrder(object):
             p_code[k] = pack_keys.setdefault(substrate_kind(packed[-1].substrate), len(pack_keys))
         freq = np.array([float(s.frequency) for s in sensors])
         code = s_code[sens_idx] * len(pack_keys) + p_code[pack_idx]
-        sol = _Solution(self, sensors, packs, sens_idx, pack_idx)
-        ctx = get_context((self.devices or [None])[0])
+        sol = self._solution_class()(self, sensors, packs, sens_idx, pack_idx)
+        ctx = self._context()
         self.launches, self.launch_info = 0, []
         for g in np.unique(code):
             sel = np.nonzero(code == g)[0]
@@ -195,14 +216,13 @@ class SuccessiveOrder(object):
             pairs = inv_f * len(u_packs) + inv_p
             full = len(pairs) == batch.n_pairs and np.array_equal(pairs, np.arange(batch.n_pairs))
             with ctx.lock:
-                out = ctx.successive_order_run(batch, self.n_iteration_max, self.relative_tolerance,
-                                               pairs=None if full else pairs, workspace_budget=self.workspace_budget)
-                self.launch_info.append(ctx.successive_order_launch_info())
+                out, info = self._run(ctx, batch, sensor0, None if full else pairs)
+                self.launch_info.append(info)
             self.launches += 1
             bad = np.nonzero(out.status != 0)[0]
             if len(bad) and self.error_handling == "exception":
                 st = int(out.status[bad[0]])
-                message = STATUS_MESSAGES.get(st, f"the successive_order solver failed with status {st}")
+                message = STATUS_MESSAGES.get(st, f"the {self._NAME} solver failed with status {st}")
                 raise SMRTError(message.replace("N sublayers", f"{int(out.sublayers[bad[0]].sum())} sublayers"))
             sol.add_group(sel, out, sps[0], (u_packs, np.array(batch.n_layers, np.int64), np.array(batch.thickness, float)))
         return sol
