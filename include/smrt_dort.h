@@ -503,6 +503,67 @@ int32_t smrt_first_order_kernel_ms(smrt_dort_ctx* ctx, double* ms2);
 int32_t smrt_first_order_abi(int32_t* out, int32_t capacity);
 
 /*
+ * The iterative second-order backscatter solver (the reference's smrt/rtsolver/iterative_second_order.py: Karam et al. 1995
+ * eqs. A8, A11, A13) on the same context: the first-order solver above plus double scattering inside a layer, volume
+ * scattering combined with the diffuse reflection of the substrate, and (optionally) double scattering between two layers.
+ * Active sensors only, V and H, no atmosphere.  Of the smrt_batch it reads what the first-order solver reads, plus
+ * n_max_stream (2 to 1024: the quadrature cosines per layer, stream_mode "most_refringent") and m_max (1 to 8: azimuth modes
+ * 0 .. m_max - 1 are summed, and m_max sets the number of azimuth samples of the IBA phase function, as in the reference);
+ * everything the first-order solver ignores is ignored.  Layers of kind SMRT_EM_HOST are refused.  An upload replaces the
+ * resident batch of the first-order solver on this context.  The struct smrt_second_order_extras may be NULL (no interlayer
+ * term, default budget, Flat interfaces, a substrate without diffuse reflection); arrays are indexed by the global pair
+ * f * S + s.
+ *   compute_scattering_interlayer  0 / 1: the O(L^2) interlayer term; its kernel is launched only when set;
+ *   workspace_budget_bytes   everything this solver reserves beyond the first-order buffers stays inside it (<= 0: 8 GiB):
+ *                            outputs, the carry, the substrate modes and, per chunk of pairs, stream sets and integrals
+ *                            (n_layers_max x n_theta x (2 + n_layers_max with the interlayer term) x 4 doubles per pair).
+ *                            The launch solves chunk after chunk; a budget smaller than the fixed buffers plus one pair
+ *                            fails the upload;
+ *   first_order              the first-order extras (host-evaluated interfaces / substrate), or NULL.  Only Flat or
+ *                            Transparent inner interfaces are meaningful: this solver has no term for diffuse reflection
+ *                            at an inner interface;
+ *   substrate_diffuse_modes  [F * S][n_layers_max][n_theta][n_max_stream][m_max][2][2][3], or NULL (no diffuse reflection
+ *                            at the substrate): for layer l, incidence angle t (cosine mu in the layer), the layer's j-th
+ *                            stream cosine mu' in ASCENDING order (entries past the layer's stream count are not read) and
+ *                            azimuth mode m, rows V, H (3 columns V, H, U) of the substrate's ft_even_diffuse_reflection_matrix
+ *                            (3 polarisations, already over 4 pi) at [0]: (scattered -mu, incident mu') and [1]: (scattered
+ *                            mu', incident mu), evaluated with the permittivity of the LAST layer, as the reference does.
+ * Outputs, one row per pair: out [7][n_theta][2][2] = the four first-order contributions (bit-identical to
+ * smrt_first_order_*), then order2_intralayer_scattering, order2_rough_layer_scattering, order2_interlayer_scattering;
+ * status; optional layer_out and diag as the first-order solver's; backscatter_layer [n_layers_max + 1][n_theta][2][2] =
+ * order 1 + order 2 per layer as the reference sums them (the order-2 part of a layer is the running sum of the two
+ * non-interlayer terms down to it, times 4 pi x its cosine).
+ */
+typedef struct smrt_second_order_extras {
+    int32_t compute_scattering_interlayer;
+    int32_t reserved;
+    int64_t workspace_budget_bytes;
+    const smrt_first_order_extras* first_order;
+    const double* substrate_diffuse_modes;
+} smrt_second_order_extras;
+
+/* Doubles per pair of `out`: 28 x n_theta. */
+int32_t smrt_second_order_out_stride(const smrt_batch* b);
+/* One shot over the listed pairs (semantics of smrt_dort_run_pairs; pairs == NULL: every pair of the batch in order,
+ * n_pairs ignored). */
+int32_t smrt_second_order_run_pairs(smrt_dort_ctx* ctx, const smrt_batch* batch, const smrt_second_order_extras* extras,
+                                    const int64_t* pairs, int64_t n_pairs, double* out, int32_t* status, double* layer_out,
+                                    double* backscatter_layer, double* diag);
+/* Split form, as smrt_first_order_*: upload once, launch (asynchronous) any number of times, sync, download (any pointer may
+ * be NULL). */
+int32_t smrt_second_order_upload_pairs(smrt_dort_ctx* ctx, const smrt_batch* batch, const smrt_second_order_extras* extras,
+                                       const int64_t* pairs, int64_t n_pairs);
+int32_t smrt_second_order_launch(smrt_dort_ctx* ctx);
+int32_t smrt_second_order_sync(smrt_dort_ctx* ctx);
+int32_t smrt_second_order_download(smrt_dort_ctx* ctx, double* out, int32_t* status, double* layer_out,
+                                   double* backscatter_layer, double* diag);
+/* HIP-event time (ms) of the last launch, after a sync: ms2[0] the two first-order kernels, ms2[1] the order-2 kernels
+ * (stream sets, integrals, walk) of every chunk. */
+int32_t smrt_second_order_kernel_ms(smrt_dort_ctx* ctx, double* ms2);
+/* Self-description of smrt_second_order_extras, like smrt_dort_abi: out[0] = its size, out[1..] = the field offsets. */
+int32_t smrt_second_order_abi(int32_t* out, int32_t capacity);
+
+/*
  * The successive-order-of-scattering solver (the reference's smrt/rtsolver/successive_order.py: Lenoble et al. 2007 eq. 66,
  * Greenwald et al. 2005 eq. 2) on the same context.  Passive sensors only, Flat interfaces, no atmosphere, emmodels with a
  * device implementation.  The batch is the smrt_batch of DORT: layers, kinds, wet snow, frequencies, theta, n_max_stream

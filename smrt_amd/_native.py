@@ -290,6 +290,51 @@ class FirstOrderOutput:
                 _dptr(self.layer_backscatter), _dptr(self.diag))
 
 
+class SecondOrderExtras(C.Structure):
+    """struct smrt_second_order_extras of include/smrt_dort.h."""
+
+    _fields_ = [
+        ("compute_scattering_interlayer", C.c_int32),
+        ("reserved", C.c_int32),
+        ("workspace_budget_bytes", C.c_int64),
+        ("first_order", C.POINTER(FirstOrderExtras)),
+        ("substrate_diffuse_modes", C.POINTER(C.c_double)),
+    ]
+
+
+class PackedSecondOrderExtras:
+    """What the iterative second-order solver needs beyond a PackedBatch (include/smrt_dort.h: smrt_second_order_extras), for a
+    batch of `n_pairs` = F * S pairs: the interlayer switch, the workspace budget (None: the library's default), the
+    first-order extras (a PackedFirstOrderExtras or None) and, for a substrate with diffuse reflection, substrate_modes
+    [F*S][Lmax][n_theta][n_max_stream][m_max][2][2][3]."""
+
+    def __init__(self, batch, interlayer=False, workspace_budget=None, first_order=None, substrate_modes=None):
+        x = SecondOrderExtras()
+        x.compute_scattering_interlayer = 1 if interlayer else 0
+        x.workspace_budget_bytes = int(workspace_budget or 0)
+        self.first_order = first_order
+        if first_order is not None:
+            x.first_order = C.pointer(first_order.struct)
+        if substrate_modes is not None:
+            b = batch.struct
+            shape = (batch.n_pairs, int(b.n_layers_max), int(b.n_theta), int(b.n_max_stream), int(b.m_max), 2, 2, 3)
+            modes = np.asarray(substrate_modes, np.float64)
+            if modes.size != int(np.prod(shape)):
+                raise SMRTError(f"the substrate modes must have the shape {shape}")
+            self.substrate_modes = np.ascontiguousarray(modes.reshape(shape))
+            x.substrate_diffuse_modes = _dptr(self.substrate_modes)
+        self.struct = x
+
+
+class SecondOrderOutput(FirstOrderOutput):
+    """As FirstOrderOutput with values [7 contributions][n_theta][2][2]: the four of the first order, then the three order-2
+    mechanisms; layer_backscatter is order 1 + order 2."""
+
+    def __init__(self, batch, pair_count):
+        FirstOrderOutput.__init__(self, batch, pair_count)
+        self.values = np.empty((pair_count, 7, int(batch.struct.n_theta), 2, 2))
+
+
 class SuccessiveOrderOutput:
     """Outputs of the successive-order solver for `pair_count` pairs: values [2][n_theta][n_iteration_max + 1] kelvin (the
     last entry of the order axis is the total), status, layers [Lmax][5] and streams [1 + n_max_stream] as DORT's, sublayers
@@ -467,6 +512,18 @@ def load_library():
     lib.smrt_first_order_kernel_ms.restype = C.c_int32
     lib.smrt_first_order_abi.argtypes = [P(C.c_int32), C.c_int32]
     lib.smrt_first_order_abi.restype = C.c_int32
+    X2 = P(SecondOrderExtras)
+    lib.smrt_second_order_out_stride.argtypes = [P(SmrtBatch)]
+    lib.smrt_second_order_run_pairs.argtypes = [C.c_void_p, P(SmrtBatch), X2, P(C.c_int64), C.c_int64, P(C.c_double), P(C.c_int32),
+                                                P(C.c_double), P(C.c_double), P(C.c_double)]
+    lib.smrt_second_order_upload_pairs.argtypes = [C.c_void_p, P(SmrtBatch), X2, P(C.c_int64), C.c_int64]
+    lib.smrt_second_order_launch.argtypes = [C.c_void_p]
+    lib.smrt_second_order_sync.argtypes = [C.c_void_p]
+    lib.smrt_second_order_download.argtypes = [C.c_void_p, P(C.c_double), P(C.c_int32), P(C.c_double), P(C.c_double), P(C.c_double)]
+    lib.smrt_second_order_kernel_ms.argtypes = [C.c_void_p, P(C.c_double)]
+    lib.smrt_second_order_abi.argtypes = [P(C.c_int32), C.c_int32]
+    for name in ("out_stride", "run_pairs", "upload_pairs", "launch", "sync", "download", "kernel_ms", "abi"):
+        getattr(lib, "smrt_second_order_" + name).restype = C.c_int32
     so_out = [P(C.c_double), P(C.c_int32), P(C.c_double), P(C.c_double), P(C.c_int32), P(C.c_double), P(C.c_int32)]
     lib.smrt_successive_order_out_stride.argtypes = [P(SmrtBatch), C.c_int32]
     lib.smrt_successive_order_out_stride.restype = C.c_int32
@@ -543,6 +600,23 @@ def check_struct_layout(lib):
     if mine != theirs:
         raise SMRTError(f"smrt_first_order_extras layout mismatch between smrt_amd/_native.py {mine} and {LIB_PATH} {theirs}: "
                         "rebuild the library or update the binding (include/smrt_dort.h)")
+    mine, theirs = second_order_extras_layout(), second_order_abi_layout(lib)
+    if mine != theirs:
+        raise SMRTError(f"smrt_second_order_extras layout mismatch between smrt_amd/_native.py {mine} and {LIB_PATH} {theirs}: "
+                        "rebuild the library or update the binding (include/smrt_dort.h)")
+
+
+def second_order_extras_layout():
+    """[sizeof, field offsets] of the ctypes declaration of smrt_second_order_extras."""
+    return [C.sizeof(SecondOrderExtras)] + [getattr(SecondOrderExtras, name).offset for name, _ in SecondOrderExtras._fields_]
+
+
+def second_order_abi_layout(lib):
+    """The same as the library was compiled (smrt_second_order_abi)."""
+    n = lib.smrt_second_order_abi(None, 0)
+    a = (C.c_int32 * n)()
+    lib.smrt_second_order_abi(a, n)
+    return list(a)
 
 
 def first_order_extras_layout():
@@ -567,6 +641,8 @@ EXPORTED_SYMBOLS = [
     "smrt_dort_version", "smrt_dort_finish_reg_lds_bytes", "smrt_dort_finish_strip_lds_bytes", "smrt_dort_jacobi_lds_bytes", "smrt_dort_gather_plan",
     "smrt_first_order_out_stride", "smrt_first_order_run_pairs", "smrt_first_order_upload_pairs", "smrt_first_order_launch",
     "smrt_first_order_sync", "smrt_first_order_download", "smrt_first_order_kernel_ms", "smrt_first_order_abi",
+    "smrt_second_order_out_stride", "smrt_second_order_run_pairs", "smrt_second_order_upload_pairs", "smrt_second_order_launch",
+    "smrt_second_order_sync", "smrt_second_order_download", "smrt_second_order_kernel_ms", "smrt_second_order_abi",
     "smrt_successive_order_out_stride", "smrt_successive_order_run_pairs", "smrt_successive_order_upload_pairs",
     "smrt_successive_order_launch", "smrt_successive_order_sync", "smrt_successive_order_download",
     "smrt_successive_order_kernel_ms", "smrt_successive_order_launch_info",
@@ -740,6 +816,43 @@ class DortContext:
         """HIP-event ms of the (pair, layer) kernel and of the (pair, angle) kernel of the last launch."""
         a = np.zeros(2)
         self._check(self._lib.smrt_first_order_kernel_ms(self._h, _dptr(a)), "smrt_first_order_kernel_ms")
+        return float(a[0]), float(a[1])
+
+    # ---- the iterative second-order solver (smrt_second_order_*): it replaces the resident first-order batch ----------
+    def second_order_run(self, batch: PackedBatch, extras=None, pairs=None) -> SecondOrderOutput:
+        """One shot (H2D, kernels, D2H) for every pair of the batch or the listed ones (row i = pairs[i])."""
+        args, pairs = self._first_order_args(batch, extras, pairs)
+        o = SecondOrderOutput(batch, batch.n_pairs if pairs is None else len(pairs))
+        with self.lock:
+            self._check(self._lib.smrt_second_order_run_pairs(self._h, *args, *o.pointers()), "smrt_second_order_run_pairs")
+        return o
+
+    def second_order_upload(self, batch: PackedBatch, extras=None, pairs=None):
+        """Split form (upload once, launch any number of times, sync, download); see first_order_upload for the lock."""
+        args, pairs = self._first_order_args(batch, extras, pairs)
+        with self.lock:
+            self._check(self._lib.smrt_second_order_upload_pairs(self._h, *args), "smrt_second_order_upload_pairs")
+            self._second_order_resident = (batch, extras, pairs, batch.n_pairs if pairs is None else len(pairs))
+
+    def second_order_launch(self):
+        with self.lock:
+            self._check(self._lib.smrt_second_order_launch(self._h), "smrt_second_order_launch")
+
+    def second_order_sync(self):
+        with self.lock:
+            self._check(self._lib.smrt_second_order_sync(self._h), "smrt_second_order_sync")
+
+    def second_order_download(self) -> SecondOrderOutput:
+        with self.lock:
+            batch, _, _, n = self._second_order_resident
+            o = SecondOrderOutput(batch, n)
+            self._check(self._lib.smrt_second_order_download(self._h, *o.pointers()), "smrt_second_order_download")
+        return o
+
+    def second_order_kernel_ms(self):
+        """HIP-event ms of the first-order kernels and of the order-2 kernels of the last launch."""
+        a = np.zeros(2)
+        self._check(self._lib.smrt_second_order_kernel_ms(self._h, _dptr(a)), "smrt_second_order_kernel_ms")
         return float(a[0]), float(a[1])
 
     # ---- the successive-order solver (smrt_successive_order_*) ----------------------------------------------------

@@ -8,7 +8,7 @@
 
 #include "dort_layout.hpp"
 
-namespace smrt { struct PhaseRequest; }
+namespace smrt { struct PhaseRequest; struct FoBatch; }
 
 struct DevBuf {
     void* p = nullptr;
@@ -92,6 +92,8 @@ struct smrt_dort_ctx {
     struct SuccessiveOrderActiveState* successive_order_active = nullptr;
     // the multi-Fresnel thermal emission solver (multifresnel.hip): likewise
     struct MultiFresnelState* multifresnel = nullptr;
+    // the iterative second-order solver (second_order.hip): likewise; its orders 0 and 1 are `first_order`'s
+    struct SecondOrderState* second_order = nullptr;
 };
 
 #ifndef SMRT_JACOBI_NT
@@ -144,4 +146,9 @@ void successive_order_release(smrt_dort_ctx* ctx);
 void successive_order_active_release(smrt_dort_ctx* ctx);
 // multifresnel.hip: frees ctx->multifresnel (smrt_dort_destroy)
 void multifresnel_release(smrt_dort_ctx* ctx);
+// second_order.hip: frees ctx->second_order (smrt_dort_destroy)
+void second_order_release(smrt_dort_ctx* ctx);
+// first_order.hip: the resident batch of the first-order solver as its kernels get it (null: nothing uploaded); the
+// second-order solver sets its carry pointer and reads the staging rows and outputs
+smrt::FoBatch* first_order_resident(smrt_dort_ctx* ctx);
 }  // namespace smrt_launch

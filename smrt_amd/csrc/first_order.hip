@@ -57,6 +57,10 @@ void first_order_release(smrt_dort_ctx* ctx) {
     delete st;
     ctx->first_order = nullptr;
 }
+FoBatch* first_order_resident(smrt_dort_ctx* ctx) {
+    FirstOrderState* st = ctx->first_order;
+    return st && st->uploaded ? &st->dev : nullptr;
+}
 }  // namespace smrt_launch
 
 static int fo_upload(smrt_dort_ctx* ctx, DevBuf& buf, const void* src, size_t bytes) {

@@ -23,6 +23,9 @@ enum { FO_EPS_RE = 0, FO_EPS_IM, FO_KS, FO_KA, FO_PA, FO_PB, FO_KIND, FO_THICK, 
 // doubles per (pair, interface slot, angle) of the host-evaluated interfaces: specular reflection V, H; downward coherent
 // transmission V, H; upward coherent transmission V, H; diffuse reflection at (mu, mu, pi): vv, vh, hv, hh
 constexpr int kFoInterfaceDoubles = 10;
+// doubles per (pair, layer, angle) of the optional carry: downward intensity in the layer V, H (it stays diagonal), cumulative
+// upward transmission V, H, cosine of the incidence direction in the layer -- what second_order_kernel.hpp applies its terms to
+constexpr int kFoCarryDoubles = 5;
 
 struct FoBatch {
     int S, Lmax, F, n_theta;
@@ -43,6 +46,7 @@ struct FoBatch {
     double* layer_out;                          // [n_pairs][Lmax][5] or null
     double* layer_backscatter;                  // [n_pairs][Lmax + 1][n_theta][2][2] or null
     double* diag;                               // [n_pairs][2] or null
+    double* carry;                              // [n_pairs][Lmax][n_theta][5] or null: a store only, the results do not depend on it
 };
 
 SMRT_DEV long long fo_global_pair(const FoBatch& b, long long i) { return b.pair_map ? b.pair_map[i] : i; }
@@ -208,6 +212,10 @@ SMRT_DEV void first_order_angle_item(const FoBatch& b, long long i, int t) {
                 fresnel_RvRh(e_l, e_up, mu_l, &rv, &rh);
                 upv *= 1.0 - rv; uph *= 1.0 - rh;
             }
+        }
+        if (b.carry) {
+            double* c = b.carry + ((i * b.Lmax + l) * nt + t) * kFoCarryDoubles;
+            c[0] = I.vv; c[1] = I.hh; c[2] = upv; c[3] = uph; c[4] = mu_l;
         }
         // the boundary below: the next interface, the substrate, or nothing
         FoBoundary bot;

@@ -48,6 +48,7 @@ class IterativeFirstOrder(object):
     ("total" first, then the four mechanisms).  `devices` (list of GPU indices; the first is used) is smrt_amd's own knob."""
 
     _broadcast_capability = {"theta_inc", "polarization_inc", "theta", "polarization"}
+    NAME = "iterative_first_order"   # in the messages; a solver built on this one (iterative_second_order) sets its own
 
     def __init__(self, error_handling="exception", return_contributions=False, devices=None):
         if error_handling not in ("exception", "nan"):
@@ -66,7 +67,7 @@ class IterativeFirstOrder(object):
         self._check_sensor(sensor)
         snowpack = adopt_snowpack(snowpack)
         if atmosphere is not None or snowpack.atmosphere is not None:
-            raise SMRTError("the iterative_first_order solver can not handle atmosphere yet.")
+            raise SMRTError(f"the {self.NAME} solver can not handle atmosphere yet.")
         if len(emmodels) != snowpack.nlayer:
             raise SMRTError("one emmodel per layer is needed")
         entries = [entry_of_instance(e, layer) for e, layer in zip(emmodels, snowpack.layers)]
@@ -114,16 +115,16 @@ class IterativeFirstOrder(object):
     emmodel_names = DORT.emmodel_names
 
     # ---- grouping, packing, launching ----------------------------------------------------------------------------
-    @staticmethod
-    def _check_sensor(sensor):
+    @classmethod
+    def _check_sensor(cls, sensor):
         if sensor.mode != "A":
-            raise SMRTError("the iterative_first_order solver is only suitable for active microwave. Use an adequate sensor "
+            raise SMRTError(f"the {cls.NAME} solver is only suitable for active microwave. Use an adequate sensor "
                             "falling in this category.")
         if np.ndim(sensor.frequency) != 0:
-            raise SMRTError("the iterative_first_order solver does not broadcast the frequency: split the sensor first "
+            raise SMRTError(f"the {cls.NAME} solver does not broadcast the frequency: split the sensor first "
                             "(Model.run does)")
         if not np.array_equal(sensor.theta_deg, sensor.theta_inc_deg):
-            raise SMRTError("the iterative_first_order solver computes the backscatter (theta == theta_inc)")
+            raise SMRTError(f"the {cls.NAME} solver computes the backscatter (theta == theta_inc)")
 
     def _packer(self):
         return _Packer(n_max_stream=2, m_max=0, error_handling=self.error_handling, devices=self.devices)
@@ -139,12 +140,12 @@ class IterativeFirstOrder(object):
         p_code = np.empty(len(packs), np.int64)
         for k, sp in enumerate(packs):
             if sp.atmosphere is not None:
-                raise SMRTError("the iterative_first_order solver can not handle atmosphere yet.")
+                raise SMRTError(f"the {self.NAME} solver can not handle atmosphere yet.")
             on_host = not isinstance(emmodel_names, str) and any(not isinstance(e, str) for e in emmodel_names[k])
             p_code[k] = pack_keys.setdefault((substrate_kind(sp.substrate), on_host), len(pack_keys))
         freq = np.array([float(s.frequency) for s in sensors])
         code = s_code[sens_idx] * len(pack_keys) + p_code[pack_idx]
-        sol = _Solution(self, sensors, packs, sens_idx, pack_idx)
+        sol = self._solution(sensors, packs, sens_idx, pack_idx)
         ctx = get_context((self.devices or [None])[0])
         self.launches = 0
         for g in np.unique(code):
@@ -160,27 +161,34 @@ class IterativeFirstOrder(object):
             extras = self._extras(ctx.first_order_layers, batch, packer, sensor0, sps, u_freq)
             pairs = inv_f * len(u_packs) + inv_p
             full = len(pairs) == batch.n_pairs and np.array_equal(pairs, np.arange(batch.n_pairs))
-            out = ctx.first_order_run(batch, extras, pairs=None if full else pairs)
+            out = self._run_group(ctx, batch, extras, None if full else pairs, packer, sensor0, sps, u_freq)
             self.launches += 1
             bad = np.nonzero(out.status != 0)[0]
             if len(bad) and self.error_handling == "exception":
                 st = int(out.status[bad[0]])
-                raise SMRTError(STATUS_MESSAGES.get(st, f"the iterative_first_order solver failed with status {st}"))
+                raise SMRTError(STATUS_MESSAGES.get(st, f"the {self.NAME} solver failed with status {st}"))
             sol.add_group(sel, out, (u_packs, np.array(batch.n_layers, np.int64), np.array(batch.thickness, float)),
                           no_substrate=sps[0].substrate is None)
         sol.warn()
         return sol
 
+    # the two places a solver built on this one (iterative_second_order) differs in: the device call and the result axis
+    def _run_group(self, ctx, batch, extras, pairs, packer, sensor0, sps, freqs):
+        return ctx.first_order_run(batch, extras, pairs=pairs)
+
+    def _solution(self, sensors, packs, sens_idx, pack_idx):
+        return _Solution(self, sensors, packs, sens_idx, pack_idx)
+
     # ---- what the host evaluates (include/smrt_dort.h: smrt_first_order_extras) ------------------------------------
-    @staticmethod
-    def _rows(value, n):
+    @classmethod
+    def _rows(cls, value, n):
         """[2, n] from a diagonal reflection / transmission 'matrix' of the interface protocol (0 -> zeros)."""
         a = np.asarray(getattr(value, "values", value), float)
         if a.ndim == 0:
             return np.full((2, n), float(a))
         if a.ndim == 2 and a.shape[0] >= 2 and a.shape[1] == n:
             return a[:2]
-        raise SMRTError(f"the iterative_first_order solver needs diagonal specular / coherent matrices [npol, n_mu], got {a.shape}")
+        raise SMRTError(f"the {cls.NAME} solver needs diagonal specular / coherent matrices [npol, n_mu], got {a.shape}")
 
     @staticmethod
     def _dense(value, n):

@@ -34,6 +34,8 @@ def ctype_of(decl):
         return "C.c_void_p"
     if base == "smrt_first_order_extras":   # {int32 slots, int32 reserved, three pointers}: optional, passed as an opaque pointer (or None)
         return "C.c_void_p"
+    if base == "smrt_second_order_extras":   # {int32 interlayer, int32 reserved, int64 budget, two pointers}: likewise
+        return "C.c_void_p"
     c = SCALARS[base]
     for _ in range(stars):
         c = "C.POINTER(%s)" % c
