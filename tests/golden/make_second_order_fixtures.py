@@ -8,7 +8,9 @@ the layer scalars (the inputs are the case table itself).  It fails unless each 
 1 % of the largest co-polarised total in at least one case, unless HV of the total is non-zero wherever a layer scatters,
 and unless at least one interlayer value is negative (the finding of DESIGN.md section 4f).
 
-    PYTHONDONTWRITEBYTECODE=1 python tests/golden/make_second_order_fixtures.py
+    PYTHONDONTWRITEBYTECODE=1 python tests/golden/make_second_order_fixtures.py [NAME ...]
+
+With names only those cases are run and written (the conditions on the whole set are then not checked).
 """
 import contextlib
 import io
@@ -40,10 +42,14 @@ API = types.SimpleNamespace(make_snowpack=make_snowpack, make_interface=make_int
                             transparent_substrate=lambda: make_soil("transparent", complex(1.0, 1e-6), 270.0))
 
 
-def main():
+def main(names=()):
     largest_share = np.zeros(3)
     most_negative = 0.0
+    unknown = set(names) - {c["name"] for c in CASES}
+    assert not unknown, f"no such case: {sorted(unknown)}"
     for case in CASES:
+        if names and case["name"] not in names:
+            continue
         sp = build_snowpack(case, API)
         model = make_model(case["emmodel"], "iterative_second_order", rtsolver_options=dict(return_contributions=True, **options_of(case)))
         with contextlib.redirect_stdout(io.StringIO()):   # the reference's geometrical optics prints on every call
@@ -64,6 +70,8 @@ def main():
                  eps=np.asarray(other["effective_permittivity"].values, complex), ks=ks, ka=np.asarray(other["ka"].values, float))
         print(case["name"], "sigmaVV dB:", np.round(10 * np.log10(4 * np.pi * np.cos(np.deg2rad(case["theta"])) * data[0, :, 0, 0]), 3),
               "order-2 shares:", np.round(shares, 4), "HV/VV:", np.round(data[0, :, 0, 1] / data[0, :, 0, 0], 4))
+    if names:
+        return
     print("largest share of the total per order-2 mechanism:", dict(zip(CONTRIBUTIONS[5:], np.round(largest_share, 4))))
     print("most negative interlayer value:", most_negative)
     assert np.all(largest_share > 0.01), "every order-2 mechanism must exceed 1 % of the total in at least one fixture"
@@ -71,4 +79,4 @@ def main():
 
 
 if __name__ == "__main__":
-    main()
+    main(sys.argv[1:])

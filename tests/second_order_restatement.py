@@ -71,6 +71,38 @@ CASES = [
          n_max_stream=8, m_max=3),
 ]
 
+# ---- the edge cases: shapes at which the device's own choices (streams on 64 lanes, the mode table of M in {2, 3, 5, 8}
+# registers, substrate rows per stream) take another path.  tests/test_second_order_cpu.py:test_edge_fixtures_are_sensitive
+# holds each to the condition that makes it able to fail.
+FLAT_SOIL = dict(substrate_model="flat", **SOIL)
+_L2 = dict(emmodel="iba", frequency=13e9, theta=[25.0, 40.0], thickness=[0.4, 0.8], density=[250.0, 380.0],
+           temperature=[260.0, 262.0], microstructure_model="exponential", corr_length=[3e-4, 8e-4])
+# a light layer, nearly solid ice, a light layer: the ice keeps every stream, its neighbours lose about half of theirs; coarse
+# enough below the top layer for the streams past the 64th to carry more than 1000 SIGMA_RTOL of the total
+_CONTRAST = dict(emmodel="iba", frequency=13e9, theta=[25.0, 40.0], thickness=[0.3, 0.2, 0.5], density=[200.0, 850.0, 300.0],
+                 temperature=[258.0, 261.0, 264.0], microstructure_model="exponential", corr_length=[3e-4, 1e-3, 8e-4])
+# thin layers of coarse grains at 37 GHz over a smooth rough soil, steep incidence: azimuth modes up to 7 are all above
+# 100 SIGMA_RTOL of the total in the intralayer and the substrate terms (the figures: test_edge_fixtures_are_sensitive)
+_MODES = dict(emmodel="iba", frequency=37e9, theta=[40.0, 60.0], thickness=[0.01, 0.01], density=[250.0, 380.0],
+              temperature=[258.0, 262.0], microstructure_model="exponential", corr_length=[1e-3, 1.5e-3],
+              substrate=dict(substrate_model="geometrical_optics", mean_square_slope=0.003, **SOIL), n_max_stream=8,
+              interlayer=True)
+_RAYLEIGH = next(dict(c) for c in CASES if c["name"] == "rayleigh_L2_flat")
+EDGE_CASES = [
+    dict(name="iba_exp_L2_n64_inter", substrate=FLAT_SOIL, n_max_stream=64, m_max=3, interlayer=True, **_L2),
+    dict(name="iba_exp_L2_n65_inter", substrate=FLAT_SOIL, n_max_stream=65, m_max=3, interlayer=True, **_L2),
+    dict(name="iba_exp_contrast_L3_n130_inter", substrate=FLAT_SOIL, n_max_stream=130, m_max=2, interlayer=True, **_CONTRAST),
+    dict(name="iba_exp_contrast_L3_go_n16_inter", substrate=GO_SOIL, n_max_stream=16, m_max=3, interlayer=True, **_CONTRAST),
+] + [dict(name=f"iba_exp_L2_go_m{k}", m_max=k, **_MODES) for k in (1, 4, 6, 7, 8)] + [
+    dict(_RAYLEIGH, name="rayleigh_L2_flat_m8", m_max=8),
+    dict(_RAYLEIGH, name="rayleigh_L2_flat_m2", m_max=2),
+    dict(name="iba_exp_L1_inter", emmodel="iba", frequency=13e9, theta=[25.0, 40.0], thickness=[0.6], density=[300.0],
+         temperature=[260.0], microstructure_model="exponential", corr_length=[3e-4], substrate=FLAT_SOIL, n_max_stream=8, m_max=3,
+         interlayer=True),
+]
+EDGE_NAMES = [c["name"] for c in EDGE_CASES]
+CASES += EDGE_CASES
+
 
 def options_of(case):
     return dict(n_max_stream=case["n_max_stream"], m_max=case["m_max"],
@@ -162,8 +194,10 @@ def has_diffuse_modes(obj):
 
 # ---- the solution ------------------------------------------------------------------------------------------------------
 def second_order(layers, thickness, frequency, theta_deg, interfaces=None, substrate=None, n_max_stream=32, m_max=5,
-                 interlayer=False):
-    """(contributions [7, n, 2, 2], backscatter_layer [L + 1, n, 2, 2]) for oracle layers."""
+                 interlayer=False, stream_limit=None):
+    """(contributions [7, n, 2, 2], backscatter_layer [L + 1, n, 2, 2]) for oracle layers.  `stream_limit` (tests only):
+    every layer's stream set, ascending, is cut to its first `stream_limit` entries AFTER the weights are made -- what a
+    wavefront computes whose lanes never take a second trip over the streams."""
     L = len(layers)
     first, per_layer1 = FO.first_order(layers, thickness, frequency, theta_deg, interfaces, substrate)
     theta = np.deg2rad(np.atleast_1d(np.asarray(theta_deg, float)))
@@ -173,8 +207,8 @@ def second_order(layers, thickness, frequency, theta_deg, interfaces=None, subst
     interfaces = interfaces or [None] * L
     eps = [1.0 + 0j] + [complex(lay.eps_eff) for lay in layers]
     st = O.compute_streams(n_max_stream, np.array(eps[1:]))
-    smu = [m[::-1] for m in st.mu]
-    sw = [w[::-1] for w in st.weight]
+    smu = [m[::-1][:stream_limit] for m in st.mu]
+    sw = [w[::-1][:stream_limit] for w in st.weight]
     ke = [lay.ks + lay.ka for lay in layers]
     tau = [k * d for k, d in zip(ke, thickness)]
     rough = has_diffuse_modes(substrate)
@@ -219,7 +253,7 @@ def second_order(layers, thickness, frequency, theta_deg, interfaces=None, subst
     return out, per_layer
 
 
-def solve_case(case, snowpack, emmodel_names=None):
+def solve_case(case, snowpack, emmodel_names=None, stream_limit=None):
     """The restatement on a fixture case; `snowpack`: the package's Snowpack built by build_snowpack."""
     wet = None
     if "volumetric_liquid_water" in case:
@@ -230,4 +264,4 @@ def solve_case(case, snowpack, emmodel_names=None):
     if spec and spec.get("substrate_model") == "flat":
         sub = ("flat", spec["permittivity_model"])
     return second_order(layers, case["thickness"], case["frequency"], case["theta"], interfaces, sub, case["n_max_stream"],
-                        case["m_max"], bool(case.get("interlayer"))), layers
+                        case["m_max"], bool(case.get("interlayer")), stream_limit), layers

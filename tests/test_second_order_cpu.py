@@ -6,7 +6,9 @@ restatement on a random batch.
 Tolerance: every contribution, every backscatter_layer entry and the total within SIGMA_RTOL = 1e-8 of the solve's largest
 co-polarised total (the project's bar for sigma0), against the fixtures and against the restatement alike."""
 import ctypes as C
+import functools
 import os
+import re
 import subprocess
 import types
 
@@ -377,30 +379,56 @@ def test_fiber_order_does_not_matter(host_ctx):
         host_ctx.order = 0
 
 
-def random_batch(rng, layer_counts, theta_deg, n_max_stream=6, m_max=3):
-    """Snowpacks of the given layer counts (IBA, exponential, Flat substrate) as (cases, PackedBatch ingredients)."""
+def random_batch(rng, layer_counts, theta_deg, n_max_stream=6, m_max=3, density=(200.0, 420.0), substrate=None):
+    """Snowpacks of the given layer counts (IBA, exponential) as cases.  `density`: the range the densities are drawn from;
+    `substrate`: None (a Flat soil under every snowpack) or a function of the snowpack's index that gives its soil."""
     cases = []
     for k, L in enumerate(layer_counts):
         cases.append(dict(name=f"random_{k}", emmodel="iba", frequency=13e9, theta=list(theta_deg), thickness=list(rng.uniform(0.1, 0.6, L)),
-                          density=list(rng.uniform(200.0, 420.0, L)), temperature=list(rng.uniform(250.0, 270.0, L)),
+                          density=list(rng.uniform(density[0], density[1], L)), temperature=list(rng.uniform(250.0, 270.0, L)),
                           microstructure_model="exponential", corr_length=list(rng.uniform(1e-4, 4e-4, L)),
-                          substrate=dict(substrate_model="flat", **R.SOIL), n_max_stream=n_max_stream, m_max=m_max))
+                          substrate=substrate(k) if substrate else dict(substrate_model="flat", **R.SOIL), n_max_stream=n_max_stream,
+                          m_max=m_max))
     return cases
 
 
-def solve_batch_on(ctx, cases, interlayer):
-    from smrt_amd.core.model import SimulationPlan
-    from smrt_amd.rtsolver.iterative_second_order import IterativeSecondOrder
+class PackedGroup:
+    """Cases (one set of angles, one n_max_stream and m_max) packed once by the solver's own packer as snowpacks x
+    `frequencies` (None: the frequency of the first case), global pair = frequency index x len(cases) + snowpack index;
+    run() sends it through the solver's own _extras and _run_group on a context, any number of times."""
 
-    sps = [build_snowpack(c, api()) for c in cases]
-    sensor = sensor_list.active(cases[0]["frequency"], cases[0]["theta"])
-    solver = IterativeSecondOrder(n_max_stream=cases[0]["n_max_stream"], m_max=cases[0]["m_max"], compute_scattering_interlayer=interlayer)
-    packer = solver._packer()
-    idx = np.arange(len(sps))
-    names = solver.emmodel_names(make_model("iba", "iterative_second_order"), SimulationPlan([sensor], sps, np.zeros(len(sps), int), idx))
-    freqs = np.array([float(cases[0]["frequency"])])
-    batch = packer._pack(sensor, sps, freqs, names, {})
-    return solver._run_group(ctx, batch, None, None, packer, sensor, sps, freqs), sps
+    def __init__(self, cases, frequencies=None):
+        from smrt_amd.core.model import SimulationPlan
+        from smrt_amd.rtsolver.iterative_second_order import IterativeSecondOrder
+
+        self.cases = cases
+        self.sps = [build_snowpack(c, api()) for c in cases]
+        self.freqs = np.array([float(f) for f in (frequencies or [cases[0]["frequency"]])])
+        self.sensor = sensor_list.active(float(self.freqs[0]), cases[0]["theta"])
+        self.solver = IterativeSecondOrder(n_max_stream=cases[0]["n_max_stream"], m_max=cases[0]["m_max"])
+        self.solver.launches = 0
+        self.host_side = None
+        self.packer = self.solver._packer()
+        idx = np.arange(len(self.sps))
+        names = self.solver.emmodel_names(make_model("iba", "iterative_second_order"),
+                                          SimulationPlan([self.sensor], self.sps, np.zeros(len(self.sps), int), idx))
+        self.batch = self.packer._pack(self.sensor, self.sps, self.freqs, names, {})
+
+    def run(self, ctx, interlayer, workspace_budget=None, pairs=None):
+        """What the host evaluates for the batch (first order's extras, the substrate's modes) depends on none of the
+        arguments but the context: evaluated by the solver's own methods on the first run on a context, kept for the next."""
+        s = self.solver
+        s.compute_scattering_interlayer, s.workspace_budget = bool(interlayer), workspace_budget
+        if self.host_side is None or self.host_side[0] is not ctx:
+            self.host_side = (ctx, s._extras(ctx.first_order_layers, self.batch, self.packer, self.sensor, self.sps, self.freqs),
+                              type(s)._substrate_modes(s, ctx, self.batch, self.sensor, self.sps, self.freqs))
+            s._substrate_modes = lambda *args: self.host_side[2]
+        return s._run_group(ctx, self.batch, self.host_side[1], pairs, self.packer, self.sensor, self.sps, self.freqs)
+
+
+def solve_batch_on(ctx, cases, interlayer, frequencies=None):
+    group = PackedGroup(cases, frequencies)
+    return group.run(ctx, interlayer), group.sps
 
 
 def test_device_arithmetic_on_a_random_batch_matches_the_restatement(host_ctx):
@@ -415,3 +443,230 @@ def test_device_arithmetic_on_a_random_batch_matches_the_restatement(host_ctx):
             assert_close(case["name"], case["theta"], out.values[k], out.layer_backscatter[k][:L + 1], np.concatenate([c.sum(axis=0)[None], c]), pl,
                          "host build, interlayer" if interlayer else "host build")
             assert not out.layer_backscatter[k][L + 1:].any()
+
+
+# ---- the edge shapes (tests/test_gpu_second_order_edges.py runs the same batches on the GPU) ------------------------------
+def test_edge_fixtures_are_sensitive():
+    """A fixture that a wrong kernel would pass proves nothing: the conditions on the inputs of the edge cases
+    (second_order_restatement.EDGE_CASES), each checked on the restatement alone.  The margins are relative to the largest
+    co-polarised total of the case, as SIGMA_RTOL is.
+
+    Streams past lane 63 -- every case with more than 64 streams in a layer, evaluated again with every layer's stream set
+    cut to its first 64 (a wavefront whose lanes take one trip only): an order-2 contribution must move by more than
+    1000 SIGMA_RTOL = 1e-5 -- the intralayer term always, the interlayer term where two layers of the snowpack both have
+    more than 64 streams (it stops at the shorter set).  Measured (intralayer / interlayer): iba_exp_L2_n65_inter, sets
+    48 / 65, 1.3e-4 / 0;  iba_exp_contrast_L3_n130_inter, sets 60 / 130 / 66, 1.4e-3 / 1.3e-4.
+
+    Top mode -- every m_max = k case with k in 4, 6, 7, 8, against the same input at m_max = k - 1: an order-2 contribution
+    must move by more than 100 SIGMA_RTOL = 1e-6.  Measured (intralayer / substrate / interlayer):
+    k = 4: 2.2e-2 / 6.9e-3 / 1.8e-3;  k = 6: 2.5e-4 / 5.9e-4 / 6.5e-6;  k = 7: 2.3e-5 / 2.3e-4 / 4.8e-7;
+    k = 8: 2.1e-6 / 8.5e-5 / 3.2e-8.  No k is dropped; the interlayer term alone would not hold k = 7 and 8.
+
+    The stream sets the cases are built for are asserted too: 47 / 64, 48 / 65, 60 / 130 / 66 and 7 / 16 / 8."""
+    from smrt_amd.rtsolver.iterative_second_order import IterativeSecondOrder
+
+    by_name = {c["name"]: c for c in R.EDGE_CASES}
+    counts = {}
+    for case in R.EDGE_CASES:
+        sp = build_snowpack(case, api())
+        (full, _), layers = solve_case(case, sp)
+        scale = scale_of(np.concatenate([full.sum(axis=0)[None], full]))
+        sets = IterativeSecondOrder.stream_sets(case["n_max_stream"], [complex(lay.eps_eff) for lay in layers])
+        counts[case["name"]] = [len(mu) for mu, _ in sets]
+        if max(counts[case["name"]]) > 64:
+            (cut, _), _ = solve_case(case, sp, stream_limit=64)
+            moved = [np.abs(full[c] - cut[c]).max() / scale for c in (4, 5, 6)]
+            print(f"{case['name']}: streams {counts[case['name']]}, cut to 64 moves intralayer {moved[0]:.2e}, substrate {moved[1]:.2e}, "
+                  f"interlayer {moved[2]:.2e}")
+            assert moved[0] > 1000 * SIGMA_RTOL, (case["name"], moved)
+            # the interlayer term stops at the shorter of two sets: it reads a stream past 64 only where both sets have one
+            n = counts[case["name"]]
+            if any(min(n[a], n[b]) > 64 for a in range(len(n)) for b in range(a + 1, len(n))):
+                assert moved[2] > 1000 * SIGMA_RTOL, (case["name"], moved)
+        k = case["m_max"]
+        if case["name"].startswith("iba_exp_L2_go_m") and k in (4, 6, 7, 8):
+            (less, _), _ = solve_case(dict(case, m_max=k - 1), sp)
+            moved = [np.abs(full[c] - less[c]).max() / scale for c in (4, 5, 6)]
+            print(f"{case['name']}: mode {k - 1} moves intralayer {moved[0]:.2e}, substrate {moved[1]:.2e}, interlayer {moved[2]:.2e}")
+            assert moved[0] > 100 * SIGMA_RTOL and moved[1] > 100 * SIGMA_RTOL, (case["name"], moved)
+    assert {n for n, c in counts.items() if max(c) > 64} == {"iba_exp_L2_n65_inter", "iba_exp_contrast_L3_n130_inter"}
+    assert counts["iba_exp_L2_n64_inter"] == [47, 64] and counts["iba_exp_L2_n65_inter"] == [48, 65]
+    assert counts["iba_exp_contrast_L3_n130_inter"] == [60, 130, 66] and counts["iba_exp_contrast_L3_go_n16_inter"] == [7, 16, 8]
+    assert {by_name[f"iba_exp_L2_go_m{k}"]["m_max"] for k in (1, 4, 6, 7, 8)} == {1, 4, 6, 7, 8}
+    # one layer with the interlayer option: the term is exactly zero
+    assert not golden(by_name["iba_exp_L1_inter"])["contributions"][7].any()
+
+
+EDGE_FREQUENCIES = (13e9, 17.25e9)
+ST_INPUT = int(re.search(r"#define SMRT_ERR_INPUT\s+(\d+)", open(os.path.join(ROOT, "include", "smrt_dort.h")).read()).group(1))
+
+
+@functools.lru_cache(maxsize=None)
+def edge_batch(which):
+    """The batches of the edge tests, as tuples of cases.
+    "frequencies": 45 snowpacks of 1, 2, 3, 4, 1, .. layers for EDGE_FREQUENCIES x 3 angles (90 pairs, 270 items of the walk:
+        a second block); two in three over a geometrical-optics soil whose mean square slope is the snowpack's own, the third
+        over the Transparent substrate (its rows of the substrate table are zero).  Not Flat: a packed batch has ONE
+        substrate kind (smrt_batch.substrate_kind; the solver groups snowpacks by it before it packs); these two are both
+        evaluated by the caller, and the other rough soils refuse the bistatic modes this solver asks for.
+    "streams": 8 snowpacks of 1 to 3 layers, densities 200 .. 850 kg m-3, n_max_stream 130, m_max 2.
+    "two_streams": n_max_stream 2; the light layer of the middle snowpack keeps one of the two streams of the ice under it
+        (relative sines 0.75 and 1.39)."""
+    if which == "frequencies":
+        def soil(k):
+            return dict(transparent=True) if k % 3 == 2 else dict(substrate_model="geometrical_optics", mean_square_slope=0.02 + 0.002 * k, **R.SOIL)
+        return tuple(random_batch(np.random.RandomState(23), [1, 2, 3, 4] * 11 + [1], [20.0, 35.0, 50.0], 6, 3, substrate=soil))
+    if which == "streams":
+        return tuple(random_batch(np.random.RandomState(33), [1, 2, 3, 2, 3, 3, 2, 3], [25.0, 40.0], 130, 2, density=(200.0, 850.0)))
+    assert which == "two_streams"
+    cases = random_batch(np.random.RandomState(3), [1, 2, 2], [25.0, 40.0], 2, 3)
+    cases[1]["density"], cases[2]["density"] = [200.0, 850.0], [300.0, 320.0]
+    return tuple(cases)
+
+
+@functools.lru_cache(maxsize=None)
+def edge_group(which):
+    return PackedGroup(edge_batch(which), EDGE_FREQUENCIES if which == "frequencies" else None)
+
+
+@functools.lru_cache(maxsize=None)
+def edge_reference(which):
+    """The restatement on every global pair of edge_batch(which), at the pair's own frequency, interlayer term ON, computed
+    once: a list of (contributions [7, n, 2, 2], backscatter_layer, stream counts per layer), read-only.  The interlayer
+    option changes nothing but contribution 6 (second_order_restatement.second_order), so the reference with the option off
+    is this one with that row zeroed: reference8()."""
+    from smrt_amd.rtsolver.iterative_second_order import IterativeSecondOrder
+
+    cases = edge_batch(which)
+    sps = [build_snowpack(c, api()) for c in cases]
+    out = []
+    for f in (EDGE_FREQUENCIES if which == "frequencies" else (13e9,)):
+        for case, sp in zip(cases, sps):
+            layers = R.O.make_layers(case["emmodel"], f, R.oracle_snowpack(case))
+            sets = IterativeSecondOrder.stream_sets(case["n_max_stream"], [complex(lay.eps_eff) for lay in layers])
+            counts = tuple(len(mu) for mu, _ in sets)
+            if min(counts) < 2:   # nothing to restate: the solver reports such a pair by its status
+                out.append((None, None, counts))
+                continue
+            (c, pl), _ = solve_case(dict(case, frequency=f, interlayer=True), sp)
+            c.setflags(write=False)
+            pl.setflags(write=False)
+            out.append((c, pl, counts))
+    return out
+
+
+def reference8(ref, interlayer):
+    c = ref[0] if interlayer else np.concatenate([ref[0][:6], np.zeros_like(ref[0][6:])])
+    return np.concatenate([c.sum(axis=0)[None], c])
+
+
+def assert_batch_matches(out, cases, reference, interlayer, what):
+    """Every global pair of a run of the whole batch against edge_reference; returns the worst error."""
+    worst = 0.0
+    assert len(out.values) == len(reference) and not out.status.any()
+    for gp, ref in enumerate(reference):
+        case = cases[gp % len(cases)]
+        L = len(case["thickness"])
+        worst = max(worst, assert_close(f"pair {gp}", case["theta"], out.values[gp], out.layer_backscatter[gp][:L + 1], reference8(ref, interlayer),
+                                        ref[1], what))
+        assert not out.layer_backscatter[gp][L + 1:].any()
+        if not interlayer or L == 1:
+            assert not out.values[gp][6].any()
+    print(f"worst of the batch, {what}:", worst)
+    return worst
+
+
+def test_rough_pairs_of_the_frequency_batch_are_told_apart():
+    """The input condition of the two-frequency batch: the order2_rough_layer_scattering rows of any two rough pairs differ
+    by more than 1000 SIGMA_RTOL of the larger of their two scales, so a substrate row read at another pair's index -- the
+    other frequency's, a neighbour's, the row of a chunk instead of the global pair -- cannot pass; the other pairs have none."""
+    cases, ref = edge_batch("frequencies"), edge_reference("frequencies")
+    S = len(cases)
+    rough = [gp for gp in range(2 * S) if "transparent" not in cases[gp % S]["substrate"]]
+    assert len(cases) == 45 and len(rough) == 60 and [len(c["thickness"]) for c in cases[:5]] == [1, 2, 3, 4, 1]
+    for gp in set(range(2 * S)) - set(rough):
+        assert not ref[gp][0][5].any()
+    scale = {gp: scale_of(reference8(ref[gp], True)) for gp in rough}
+    closest = min(np.abs(ref[a][0][5] - ref[b][0][5]).max() / max(scale[a], scale[b]) for a in rough for b in rough if a < b)
+    print("closest two rough pairs:", closest)
+    assert closest > 1000 * SIGMA_RTOL
+
+
+@pytest.mark.parametrize("interlayer", [False, True], ids=["plain", "interlayer"])
+def test_two_frequencies_and_rough_substrates_on_the_cpu(host_ctx, interlayer):
+    """The whole two-frequency batch on the host build (which has neither chunks nor listed pairs: those are the GPU's)."""
+    out = edge_group("frequencies").run(host_ctx, interlayer)
+    assert_batch_matches(out, edge_batch("frequencies"), edge_reference("frequencies"), interlayer, "host build")
+
+
+def assert_stream_counts_straddle(reference):
+    counts = [n for ref in reference for n in ref[2]]
+    assert min(counts) < 64 and any(64 < n < 128 for n in counts) and max(counts) > 128, counts
+    # and inside one snowpack: the interlayer term stops at the shorter of two unequal sets on both sides of 64
+    assert any(min(ref[2]) < 64 < max(ref[2]) for ref in reference), counts
+
+
+def test_many_streams_in_a_batch_on_the_cpu(host_ctx):
+    assert_stream_counts_straddle(edge_reference("streams"))
+    out = edge_group("streams").run(host_ctx, True)
+    assert_batch_matches(out, edge_batch("streams"), edge_reference("streams"), True, "host build, 130 streams")
+
+
+def pack_c_abi(cases, interlayer, **struct_fields):
+    """Cases packed for the C ABI, with nothing of the solver's host side in between."""
+    from test_gpu_second_order import pack_batch
+
+    batch, extras = pack_batch(list(cases), interlayer)
+    for name, value in struct_fields.items():
+        setattr(batch.struct, name, value)
+    return batch, extras
+
+
+def assert_one_stream_is_reported(out, first_values, first_layer_backscatter):
+    """The outputs of edge_batch("two_streams"): the middle pair reports ST_INPUT, its order-2 rows are NaN and its
+    first-order rows those of the first order, bit for bit."""
+    assert ST_INPUT == 5 and "fewer than two streams" in _native.STATUS_MESSAGES[ST_INPUT]
+    assert list(out.status) == [0, ST_INPUT, 0]
+    assert np.isnan(out.values[1, 4:]).all() and np.isnan(out.layer_backscatter[1, 1:3]).all()
+    assert np.array_equal(out.values[:, :4], first_values) and np.array_equal(out.layer_backscatter[1, 0], first_layer_backscatter[1, 0])
+    for k in (0, 2):
+        assert np.isfinite(out.values[k]).all() and np.isfinite(out.layer_backscatter[k]).all() and out.values[k, 4].all()
+
+
+def test_a_layer_with_one_stream_is_reported_by_status_on_the_cpu(host_lib):
+    """The light layer of the middle snowpack keeps one stream: ST_INPUT, NaN in the order-2 rows of that pair alone.  The
+    first-order rows do not depend on the streams: those of the same batch with 8 streams, where no layer loses all but
+    one."""
+    from smrt_amd.rtsolver.iterative_second_order import IterativeSecondOrder
+
+    eps = [[complex(lay.eps_eff) for lay in R.O.make_layers("iba", 13e9, R.oracle_snowpack(c))] for c in edge_batch("two_streams")]
+    assert [[len(mu) for mu, _ in IterativeSecondOrder.stream_sets(2, e)] for e in eps] == [[2], [1, 2], [2, 2]]
+
+    def run(batch, extras):
+        o = _native.SecondOrderOutput(batch, batch.n_pairs)
+        assert host_lib.smrt_second_order_host_run(C.byref(batch.struct), C.byref(extras.struct), 0, *o.pointers()) == 0
+        return o
+
+    out = run(*pack_c_abi(edge_batch("two_streams"), True))
+    eight = run(*pack_c_abi(edge_batch("two_streams"), True, n_max_stream=8))
+    assert not eight.status.any() and np.isfinite(eight.values).all()
+    assert_one_stream_is_reported(out, eight.values[:, :4], eight.layer_backscatter)
+
+
+EDGE_ANGLE_CASE = "iba_exp_contrast_L3_go_n16_inter"
+
+
+def assert_common_angle_is_the_same(run):
+    """`run(case)` -> output of one pair.  The case with its angles, with 40 degrees alone and with five angles of which 40
+    degrees is the fourth: a unit decoded by `unit % n_theta` lands on the same numbers whatever n_theta is."""
+    case = next(c for c in CASES if c["name"] == EDGE_ANGLE_CASE)
+    assert case["theta"][1] == 40.0
+    two, one, five = run(case), run(dict(case, theta=[40.0])), run(dict(case, theta=[10.0, 25.0, 55.0, 40.0, 70.0]))
+    assert one.status[0] == 0 and five.status[0] == 0 and one.values[0, 5].all() and one.values[0, 6].all()
+    for other, t in ((two, 1), (five, 3)):
+        assert np.array_equal(one.values[0][:, 0], other.values[0][:, t])
+        assert np.array_equal(one.layer_backscatter[0][:, 0], other.layer_backscatter[0][:, t])
+
+
+def test_the_common_angle_does_not_depend_on_the_angle_count_on_the_cpu(host_ctx):
+    assert_common_angle_is_the_same(lambda case: run_case(case, host_ctx))
