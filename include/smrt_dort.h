@@ -700,6 +700,76 @@ int32_t smrt_multifresnel_download(smrt_dort_ctx* ctx, double* out, int32_t* sta
  * per-(pair, angle) kernel.  Returns 0, negative on error. */
 int32_t smrt_multifresnel_kernel_ms(smrt_dort_ctx* ctx, double* ms2);
 
+/*
+ * The nadir LRM altimetry solver (the reference's smrt/rtsolver/nadir_lrm_altimetry.py with the Brown 1977 waveform model of
+ * lrm_waveform_model.py) on the same context: the waveform of a low-rate-mode radar altimeter over a layered snowpack, first
+ * order scattering, paths along the vertical.  Of the smrt_batch it reads the layers, kinds, wet snow, frequencies and the
+ * scalars of layers evaluated by the caller (host_layer, host_iba_coeff); theta, the substrate fields and everything DORT-only
+ * are ignored; an atmosphere, host_phase and process_coherent_layers are refused.  What one group of pairs shares is in
+ * smrt_lrm_params:
+ *   altitude, pulse_bandwidth, antenna_gain, nominal_gate   the sensor's;
+ *   gamma            2 / ln 2 x sin^2(beamwidth / 2) of the circular antenna pattern;
+ *   off_nadir_angle  radians; pulse_sigma  seconds (0.513 / pulse_bandwidth);
+ *   ngate, oversampling   the waveform has ngate x oversampling sub-gates;
+ *   n_mu             incidence samples of the surface / interface echo: 1 (the fast path: one convolution with the impulse
+ *                    response in closed form) or theta_inc_sampling + 1 (the slow path), with their times t_inc [n_mu];
+ *   shift            fast path: the index of the first sub-gate at or after the nominal gate (1 <= shift < ngate x oversampling);
+ *   return_contributions  three rows (surface, interfaces, volume) instead of their sum;
+ *   return_oversampled    rows of ngate x oversampling samples instead of the mean over every gate;
+ *   skip_pfs_convolution  the vertical distribution itself (n_mu == 1 only);
+ *   sigma_surface, surface_slope   [n_snowpacks] metres / radians, or NULL (zero); sigma_surface needs n_mu == 1;
+ *   interface_values  NULL (Flat interfaces, no echo), or [n_frequencies x n_snowpacks][n_layers_max + 1][1 + n_mu] per boundary
+ *                    (slot n_layers of a pair is the substrate): the one-way power transmission at nadir (NaN: Flat, evaluated on
+ *                    the device; -1: transparent) and the echo per incidence sample, refraction and coherent part included.
+ * At equal depth a layer boundary precedes a sub-gate.  Sub-gates beyond ngate x oversampling are not computed: none reaches an
+ * output sample.
+ * Outputs, one row per pair: out [rows][samples] (smrt_lrm_out_stride doubles); status [1] SMRT_OK or SMRT_ERR_INPUT (the
+ * pair's outputs are NaN then); optional (may be NULL) z_gate [samples] (NaN below the snowpack), layer_out [n_layers_max][5]
+ * (Re eps, Im eps, ks, ka, backward scattering / eps), vertical [1, 3 or 2 n_mu + 1][ngate x oversampling] the vertical
+ * distribution before the convolution (slow path / contributions: surface rows, interface rows, volume).
+ */
+typedef struct smrt_lrm_params {
+    double altitude;
+    double pulse_bandwidth;
+    double antenna_gain;
+    double gamma;
+    double off_nadir_angle;
+    double nominal_gate;
+    double pulse_sigma;
+    int32_t ngate;
+    int32_t oversampling;
+    int32_t n_mu;
+    int32_t shift;
+    int32_t return_contributions;
+    int32_t return_oversampled;
+    int32_t skip_pfs_convolution;
+    int32_t reserved;
+    const double* t_inc;
+    const double* sigma_surface;
+    const double* surface_slope;
+    const double* interface_values;
+} smrt_lrm_params;
+/* Doubles per pair of `out`. */
+int32_t smrt_lrm_out_stride(const smrt_lrm_params* p);
+/* One shot over the listed pairs (semantics of smrt_dort_run_pairs; pairs == NULL: every pair of the batch in order,
+ * n_pairs ignored).  Returns 0, negative on error. */
+int32_t smrt_lrm_run_pairs(smrt_dort_ctx* ctx, const smrt_batch* batch, const smrt_lrm_params* params, const int64_t* pairs,
+                           int64_t n_pairs, double* out, int32_t* status, double* z_gate, double* layer_out, double* vertical);
+/* Split form: upload once, launch (asynchronous on the context's stream) any number of times, sync, download. */
+int32_t smrt_lrm_upload_pairs(smrt_dort_ctx* ctx, const smrt_batch* batch, const smrt_lrm_params* params, const int64_t* pairs,
+                              int64_t n_pairs);
+int32_t smrt_lrm_launch(smrt_dort_ctx* ctx);
+int32_t smrt_lrm_sync(smrt_dort_ctx* ctx);
+/* The layer scalars of the uploaded batch alone: runs the (pair, layer) kernel and copies layer_out [pairs][n_layers_max][5],
+ * synchronously.  It is how a caller that evaluates interfaces on the host gets the permittivities it needs, before the upload
+ * that carries interface_values. */
+int32_t smrt_lrm_layers(smrt_dort_ctx* ctx, double* layer_out);
+int32_t smrt_lrm_download(smrt_dort_ctx* ctx, double* out, int32_t* status, double* z_gate, double* layer_out, double* vertical);
+/* HIP-event time (ms) of the three kernels of the last launch, after a sync: layer scalars, vertical distribution, waveform. */
+int32_t smrt_lrm_kernel_ms(smrt_dort_ctx* ctx, double* ms3);
+/* [sizeof(smrt_lrm_params), offset of every field in declaration order] as compiled; returns the number of entries. */
+int32_t smrt_lrm_abi(int32_t* out, int32_t capacity);
+
 #if defined(__GNUC__)
 #pragma GCC visibility pop
 #endif

@@ -403,6 +403,78 @@ class MultiFresnelOutput:
         return (_dptr(self.values), i32(self.status), i32(self.layers_used), _dptr(self.tau_snowpack), _dptr(self.layers))
 
 
+class LrmParams(C.Structure):
+    """struct smrt_lrm_params of include/smrt_dort.h."""
+    _fields_ = [("altitude", C.c_double), ("pulse_bandwidth", C.c_double), ("antenna_gain", C.c_double), ("gamma", C.c_double),
+                ("off_nadir_angle", C.c_double), ("nominal_gate", C.c_double), ("pulse_sigma", C.c_double),
+                ("ngate", C.c_int32), ("oversampling", C.c_int32), ("n_mu", C.c_int32), ("shift", C.c_int32),
+                ("return_contributions", C.c_int32), ("return_oversampled", C.c_int32), ("skip_pfs_convolution", C.c_int32),
+                ("reserved", C.c_int32), ("t_inc", C.POINTER(C.c_double)), ("sigma_surface", C.POINTER(C.c_double)),
+                ("surface_slope", C.POINTER(C.c_double)), ("interface_values", C.POINTER(C.c_double))]
+
+
+class PackedLrmParams:
+    """What one group of the nadir LRM altimetry solver shares beyond its PackedBatch (include/smrt_dort.h: smrt_lrm_params).
+    sensor: an Altimeter (one frequency); t_inc: the times of the incidence samples (None or one value: the fast path);
+    sigma_surface / surface_slope: [S] metres / radians or None; interface_values: [F * S][Lmax + 1][1 + n_mu] or None."""
+
+    def __init__(self, sensor, oversampling=10, t_inc=None, return_contributions=False, return_oversampled=False,
+                 skip_pfs_convolution=False, sigma_surface=None, surface_slope=None, interface_values=None, pulse_sigma=None):
+        s = LrmParams()
+        s.altitude, s.pulse_bandwidth, s.antenna_gain = float(sensor.altitude), float(sensor.pulse_bandwidth), float(sensor.antenna_gain)
+        beamwidth = (sensor.beamwidth_alongtrack + sensor.beamwidth_acrosstrack) / 2   # a 'circular' antenna pattern
+        s.gamma = 2 / 0.6931471805599453 * np.sin(np.deg2rad(beamwidth) / 2) ** 2
+        s.off_nadir_angle, s.nominal_gate = float(sensor.off_nadir_angle), float(sensor.nominal_gate)
+        s.pulse_sigma = float(pulse_sigma) if pulse_sigma is not None else 0.513 / float(sensor.pulse_bandwidth)
+        s.ngate, s.oversampling = int(sensor.ngate), int(oversampling)
+        self.t_inc = np.ascontiguousarray(np.atleast_1d(0.0 if t_inc is None else t_inc), dtype=np.float64)
+        s.n_mu = len(self.t_inc)
+        s.t_inc = _dptr(self.t_inc)
+        # the first sub-gate at or after the nominal gate, found as the reference finds it (lrm_waveform_model.py: PFS_PTR_PDF)
+        t_gate = np.arange(0, s.ngate * s.oversampling) / (s.pulse_bandwidth * s.oversampling)
+        s.shift = int((t_gate - s.nominal_gate / s.pulse_bandwidth >= 0).argmax())
+        s.return_contributions, s.return_oversampled = int(bool(return_contributions)), int(bool(return_oversampled))
+        s.skip_pfs_convolution = int(bool(skip_pfs_convolution))
+        for name, value in (("sigma_surface", sigma_surface), ("surface_slope", surface_slope), ("interface_values", interface_values)):
+            if value is not None:
+                setattr(self, name, np.ascontiguousarray(value, dtype=np.float64))
+                setattr(s, name, _dptr(getattr(self, name)))
+        self.struct = s
+
+    @property
+    def n_samples(self):
+        return self.struct.ngate * (self.struct.oversampling if self.struct.return_oversampled else 1)
+
+    @property
+    def n_sub(self):
+        return self.struct.ngate * self.struct.oversampling
+
+    @property
+    def vertical_rows(self):
+        return 2 * self.struct.n_mu + 1 if self.struct.n_mu > 1 else 3 if self.struct.return_contributions else 1
+
+    @property
+    def rows(self):
+        return 3 if self.struct.return_contributions else self.vertical_rows if self.struct.skip_pfs_convolution else 1
+
+
+class LrmOutput:
+    """Outputs of the nadir LRM altimetry solver for `pair_count` pairs: values [rows][samples], status, z_gate [samples], layers
+    [Lmax][5] (Re eps, Im eps, ks, ka, backward scattering / eps), vertical [vertical rows][ngate x oversampling]."""
+
+    def __init__(self, batch, params, pair_count):
+        Lmax = int(batch.struct.n_layers_max)
+        self.values = np.empty((pair_count, params.rows, params.n_samples))
+        self.status = np.empty(pair_count, dtype=np.int32)
+        self.z_gate = np.empty((pair_count, params.n_samples))
+        self.layers = np.empty((pair_count, Lmax, 5))
+        self.vertical = np.empty((pair_count, params.vertical_rows, params.n_sub))
+
+    def pointers(self):
+        return (_dptr(self.values), self.status.ctypes.data_as(C.POINTER(C.c_int32)), _dptr(self.z_gate), _dptr(self.layers),
+                _dptr(self.vertical))
+
+
 _lib = None
 
 
@@ -575,6 +647,19 @@ def load_library():
     lib.smrt_multifresnel_download.restype = C.c_int32
     lib.smrt_multifresnel_kernel_ms.argtypes = [C.c_void_p, P(C.c_double)]
     lib.smrt_multifresnel_kernel_ms.restype = C.c_int32
+    lrm_out = [P(C.c_double), P(C.c_int32), P(C.c_double), P(C.c_double), P(C.c_double)]
+    lrm_in = [C.c_void_p, P(SmrtBatch), P(LrmParams), P(C.c_int64), C.c_int64]
+    lib.smrt_lrm_out_stride.argtypes = [P(LrmParams)]
+    lib.smrt_lrm_run_pairs.argtypes = lrm_in + lrm_out
+    lib.smrt_lrm_upload_pairs.argtypes = lrm_in
+    lib.smrt_lrm_launch.argtypes = [C.c_void_p]
+    lib.smrt_lrm_sync.argtypes = [C.c_void_p]
+    lib.smrt_lrm_layers.argtypes = [C.c_void_p, P(C.c_double)]
+    lib.smrt_lrm_download.argtypes = [C.c_void_p] + lrm_out
+    lib.smrt_lrm_kernel_ms.argtypes = [C.c_void_p, P(C.c_double)]
+    lib.smrt_lrm_abi.argtypes = [P(C.c_int32), C.c_int32]
+    for name in ("out_stride", "run_pairs", "upload_pairs", "launch", "sync", "layers", "download", "kernel_ms", "abi"):
+        getattr(lib, "smrt_lrm_" + name).restype = C.c_int32
     check_struct_layout(lib)
     _lib = lib
     return lib
@@ -604,6 +689,23 @@ def check_struct_layout(lib):
     if mine != theirs:
         raise SMRTError(f"smrt_second_order_extras layout mismatch between smrt_amd/_native.py {mine} and {LIB_PATH} {theirs}: "
                         "rebuild the library or update the binding (include/smrt_dort.h)")
+    mine, theirs = lrm_params_layout(), lrm_abi_layout(lib)
+    if mine != theirs:
+        raise SMRTError(f"smrt_lrm_params layout mismatch between smrt_amd/_native.py {mine} and {LIB_PATH} {theirs}: "
+                        "rebuild the library or update the binding (include/smrt_dort.h)")
+
+
+def lrm_params_layout():
+    """[sizeof, field offsets] of the ctypes declaration of smrt_lrm_params."""
+    return [C.sizeof(LrmParams)] + [getattr(LrmParams, name).offset for name, _ in LrmParams._fields_]
+
+
+def lrm_abi_layout(lib):
+    """The same as the library was compiled (smrt_lrm_abi)."""
+    n = lib.smrt_lrm_abi(None, 0)
+    a = (C.c_int32 * n)()
+    lib.smrt_lrm_abi(a, n)
+    return list(a)
 
 
 def second_order_extras_layout():
@@ -650,6 +752,8 @@ EXPORTED_SYMBOLS = [
     "smrt_so_active_sync", "smrt_so_active_download", "smrt_so_active_kernel_ms", "smrt_so_active_launch_info",
     "smrt_multifresnel_out_stride", "smrt_multifresnel_run_pairs", "smrt_multifresnel_upload_pairs", "smrt_multifresnel_launch",
     "smrt_multifresnel_sync", "smrt_multifresnel_download", "smrt_multifresnel_kernel_ms",
+    "smrt_lrm_out_stride", "smrt_lrm_run_pairs", "smrt_lrm_upload_pairs", "smrt_lrm_launch", "smrt_lrm_sync", "smrt_lrm_download",
+    "smrt_lrm_kernel_ms", "smrt_lrm_abi", "smrt_lrm_layers",
 ]
 
 
@@ -1032,6 +1136,59 @@ class DortContext:
         with self.lock:
             self._check_negative(self._lib.smrt_multifresnel_kernel_ms(self._h, _dptr(a)), "smrt_multifresnel_kernel_ms")
         return float(a[0]), float(a[1])
+
+    # ---- the nadir LRM altimetry solver (smrt_lrm_*) ----------------------------------------------------------------
+    @staticmethod
+    def _lrm_args(batch, params, pairs):
+        if pairs is not None:
+            pairs = np.ascontiguousarray(pairs, dtype=np.int64)
+        return (C.byref(batch.struct), C.byref(params.struct), pairs.ctypes.data_as(C.POINTER(C.c_int64)) if pairs is not None else None,
+                len(pairs) if pairs is not None else -1), pairs
+
+    def lrm_run(self, batch: PackedBatch, params, pairs=None) -> LrmOutput:
+        """One shot (H2D, three kernels, D2H) for every pair of the batch or the listed ones (row i = pairs[i])."""
+        args, pairs = self._lrm_args(batch, params, pairs)
+        o = LrmOutput(batch, params, batch.n_pairs if pairs is None else len(pairs))
+        with self.lock:
+            self._check_negative(self._lib.smrt_lrm_run_pairs(self._h, *args, *o.pointers()), "smrt_lrm_run_pairs")
+        return o
+
+    def lrm_upload(self, batch: PackedBatch, params, pairs=None):
+        """Split form (upload once, launch any number of times, sync, download); see first_order_upload for the lock."""
+        args, pairs = self._lrm_args(batch, params, pairs)
+        with self.lock:
+            self._check_negative(self._lib.smrt_lrm_upload_pairs(self._h, *args), "smrt_lrm_upload_pairs")
+            self._lrm_resident = (batch, params, batch.n_pairs if pairs is None else len(pairs))
+
+    def lrm_layers(self, batch: PackedBatch, params):
+        """The layer scalars [n_pairs, Lmax, 5] of the batch alone: an upload and the (pair, layer) kernel, nothing else."""
+        a = np.empty((batch.n_pairs, int(batch.struct.n_layers_max), 5))
+        with self.lock:
+            self.lrm_upload(batch, params)
+            self._check_negative(self._lib.smrt_lrm_layers(self._h, _dptr(a)), "smrt_lrm_layers")
+        return a
+
+    def lrm_launch(self):
+        with self.lock:
+            self._check_negative(self._lib.smrt_lrm_launch(self._h), "smrt_lrm_launch")
+
+    def lrm_sync(self):
+        with self.lock:
+            self._check_negative(self._lib.smrt_lrm_sync(self._h), "smrt_lrm_sync")
+
+    def lrm_download(self) -> LrmOutput:
+        with self.lock:
+            batch, params, n = self._lrm_resident
+            o = LrmOutput(batch, params, n)
+            self._check_negative(self._lib.smrt_lrm_download(self._h, *o.pointers()), "smrt_lrm_download")
+        return o
+
+    def lrm_kernel_ms(self):
+        """HIP-event ms of the three kernels of the last launch: layer scalars, vertical distribution, waveform."""
+        a = np.zeros(3)
+        with self.lock:
+            self._check_negative(self._lib.smrt_lrm_kernel_ms(self._h, _dptr(a)), "smrt_lrm_kernel_ms")
+        return tuple(float(x) for x in a)
 
     def ft_even_phase(self, emmodel, microstructure, frequency, frac_volume, temperature, p1, p2, mu_s, mu_i, m_max, npol):
         """Azimuthal modes of the phase matrix of one layer: array [npol, npol, m_max + 1, len(mu_s), len(mu_i)]."""

@@ -236,6 +236,9 @@ def adopt_snowpack(snowpack, memo=None):
                        substrate=shared(getattr(snowpack, "substrate", None), adopt_substrate),
                        atmosphere=shared(getattr(snowpack, "atmosphere", None), adopt_atmosphere))
     adopted.source = snowpack
+    for name in ("sigma_surface", "surface_slope"):   # what the altimetry solver reads of a snowpack
+        if hasattr(snowpack, name):
+            setattr(adopted, name, getattr(snowpack, name))
     memo[key] = adopted
     return adopted
 

@@ -148,7 +148,10 @@ class LabeledArray:
 NETCDF_VARIABLE = "__xarray_dataarray_variable__"   # the name xarray gives an unnamed DataArray in DataArray.to_netcdf
 
 
-def save_labeled_array(arr, filename):
+EXTRA_VARIABLES = ("z_gate",)   # further variables an AltimetryResult writes next to its data
+
+
+def save_labeled_array(arr, filename, extra=None):
     """Write a LabeledArray as a netCDF-3 file laid out like xarray's DataArray.to_netcdf (one data variable, one
     coordinate variable per dimension, strings as character arrays, attributes on the data variable), so that the
     reference's `open_result` / `xr.open_dataarray` read it.  scipy.io.netcdf_file is the only dependency."""
@@ -172,13 +175,16 @@ def save_labeled_array(arr, filename):
         data[:] = np.asarray(arr.values, dtype=np.float64)
         for k, v in arr.attrs.items():
             setattr(data, k, v)
+        for name, other in (extra or {}).items():   # on (a subset of) the dimensions of the data
+            var = nc.createVariable(name, "d", tuple(other.coords.keys()))
+            var[:] = np.asarray(other.values, dtype=np.float64)
 
 
 def load_labeled_array(filename):
     from scipy.io import netcdf_file
 
     with netcdf_file(filename, "r", mmap=False) as nc:
-        names = [n for n in nc.variables if n not in nc.dimensions]
+        names = [n for n in nc.variables if n not in nc.dimensions and n not in EXTRA_VARIABLES]
         if len(names) != 1:
             raise SMRTError(f"'{filename}' does not hold exactly one data variable")
         var = nc.variables[names[0]]
@@ -190,7 +196,12 @@ def load_labeled_array(filename):
                 v = np.array([b"".join(row).rstrip(b"\0").decode() for row in v])
             coords.append((dim, v))
         attrs = {k: (v.decode() if isinstance(v, bytes) else v) for k, v in var._attributes.items()}
-        return LabeledArray(var[:].copy(), coords, attrs=attrs)
+        data = LabeledArray(var[:].copy(), coords, attrs=attrs)
+        for name in EXTRA_VARIABLES:
+            if name in nc.variables:
+                v = nc.variables[name]
+                data.attrs[name] = LabeledArray(v[:].copy(), [(d, data.coords[d]) for d in v.dimensions], name=name)
+        return data
 
 
 def open_result(filename):
@@ -199,6 +210,9 @@ def open_result(filename):
     mode = data.attrs.get("mode")
     if mode not in ("A", "P"):
         mode = "A" if "theta_inc" in data.coords else "P"
+    if data.attrs.get("result") == "altimetry":
+        z_gate = data.attrs.pop("z_gate", None)
+        return AltimetryResult(data, z_gate=z_gate)
     return (ActiveResult if mode == "A" else PassiveResult)(data)
 
 
@@ -428,6 +442,46 @@ class ActiveResult(Result):
                 f"sigmaHV={self.sigmaHV_dB()} dB")
 
 
+class AltimetryResult(ActiveResult):
+    """The waveform of an altimeter (smrt/core/result.py: AltimetryResult): dimensions (delay, theta_inc, theta), `contribution`
+    in front with return_contributions.  `gate` is the gate number of every delay, `z_gate` the depth of every gate in the
+    snowpack (NaN below it), with the batch dimensions of the result in front."""
+
+    def __init__(self, *args, z_gate=None, **kwargs):
+        super().__init__(*args, **kwargs)
+        self.data.attrs["result"] = "altimetry"
+        if z_gate is not None:
+            self.z_gate = z_gate
+
+    @property
+    def gate(self):
+        a = self.data.attrs
+        return self.data.coords["delay"] * a["pulse_bandwidth"] + a["nominal_gate"]
+
+    def save(self, filename, netcdf_engine=None):
+        z_gate = self.__dict__.get("z_gate")
+        save_labeled_array(self.data, filename, extra={"z_gate": z_gate} if z_gate is not None else None)
+
+    def delay_doppler_map(self, name="delay_doppler_map", **kwargs):
+        if "doppler_frequency" not in self.data.dims:
+            raise SMRTError("this result has no doppler_frequency dimension")
+        return self.sigma(name=name, **kwargs)
+
+    def waveform(self, name="waveform", **kwargs):
+        """The waveform; with return_contributions the total unless contribution="all" or one of them is asked for."""
+        if kwargs.get("contribution") == "all":
+            del kwargs["contribution"]
+        elif "contribution" not in kwargs and "contribution" in self.data.dims:
+            kwargs["contribution"] = "total"
+        return self.sigma(name=name, **kwargs)
+
+    def contributions(self):
+        return self.data.coords["contribution"]
+
+    def __repr__(self):
+        return f"AltimetryResult: dims={self.data.dims}, shape={self.data.shape}"
+
+
 def make_result(sensor, *args, **kwargs):
     """smrt/core/result.py:79-90."""
     if sensor.mode == "A":
@@ -460,4 +514,7 @@ def concat_results(result_list, coord):
                 channel_map[ch] = {**config, "dim_name": label}
     data = stack_arrays([r.data for r in results], dim_name, labels)
     other = {key: stack_arrays([r.other_data[key] for r in results], dim_name, labels) for key in results[0].other_data}
-    return kind(data, channel_map=channel_map, other_data=other)
+    out = kind(data, channel_map=channel_map, other_data=other)
+    if all("z_gate" in r.__dict__ for r in results):
+        out.z_gate = stack_arrays([r.z_gate for r in results], dim_name, labels)
+    return out

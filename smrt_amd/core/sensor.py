@@ -17,6 +17,8 @@ import numpy as np
 from .error import SMRTError, smrt_warn
 from .globalconstants import C_SPEED
 
+EARTH_RADIUS = 6371000.0   # volumetric mean radius of the Earth, metres
+
 AXES = ("frequency", "theta_inc", "polarization_inc", "theta", "phi", "polarization")
 _ANGLE_AXES = {"theta": ("theta_deg", "mu_s"), "theta_inc": ("theta_inc_deg", "mu_i"), "phi": ("phi_deg", None)}
 
@@ -178,6 +180,53 @@ class SensorList(SensorBase):
         if axis not in (None, self.axis):
             raise SMRTError("SensorList is unable to iterate over a different axis than its axis")
         return iter(self.sensor_list)
+
+
+class Altimeter(Sensor):
+    """A low-rate-mode radar altimeter (smrt/core/sensor.py: Altimeter).  Prefer `lrm_altimeter()` or the catalogue in
+    smrt_amd.inputs.lrm_altimeter_list.  Angles of the beam widths, pitch and roll in degrees; pitch_angle, roll_angle and
+    off_nadir_angle are in radians."""
+
+    def __init__(self, frequency, altitude, pulse_bandwidth, beamwidth_alongtrack, beamwidth_acrosstrack,
+                 pulse_repetition_frequency=0, velocity=0, antenna_gain=1, ngate=128, ndoppler=0, nominal_gate=40,
+                 doppler_window="rect", pitch_angle_deg=0.0, roll_angle_deg=0.0, theta_inc_deg=0.0, polarization_inc=None,
+                 polarization=None, channel=None):
+        super().__init__(frequency=frequency, theta_inc_deg=theta_inc_deg, theta_deg=theta_inc_deg, phi_deg=180,
+                         polarization_inc=polarization_inc, polarization=polarization,
+                         channel_map={channel: dict()} if channel is not None else dict())
+        self.altitude = altitude
+        self.beamwidth_alongtrack, self.beamwidth_acrosstrack = beamwidth_alongtrack, beamwidth_acrosstrack
+        self.antenna_gain = antenna_gain
+        self.pulse_repetition_frequency, self.velocity = pulse_repetition_frequency, velocity
+        self.ngate, self.ndoppler = ngate, ndoppler
+        self.pulse_bandwidth = pulse_bandwidth
+        self.nominal_gate = nominal_gate
+        self.pitch_angle, self.roll_angle = np.deg2rad(pitch_angle_deg), np.deg2rad(roll_angle_deg)
+        self.doppler_window = doppler_window
+        self.alpha = 1 + altitude / EARTH_RADIUS   # Earth sphericity compensation (Chelton 1989)
+
+    @property
+    def burst_duration(self):
+        return self.ndoppler / self.pulse_repetition_frequency
+
+    @property
+    def off_nadir_angle(self):
+        return np.arccos(np.cos(self.pitch_angle) * np.cos(self.roll_angle))
+
+
+def lrm_altimeter(channel=None, **kwargs):
+    """A generic LRM altimeter: the arguments of `Altimeter` by keyword."""
+    sensor = Altimeter(channel=channel, **kwargs)
+    sensor.basic_checks()
+    return sensor
+
+
+def make_multi_channel_altimeter(config, channel):
+    """The altimeter of one channel of `config` (channel name -> Altimeter arguments), or the SensorList of the listed ones
+    (None: all of them)."""
+    if isinstance(channel, str):
+        return lrm_altimeter(channel=channel, **config[channel])
+    return SensorList([lrm_altimeter(channel=ch, **config[ch]) for ch in (channel if channel is not None else config)])
 
 
 def passive(frequency, theta, polarization=None, channel_map=None, name=None):

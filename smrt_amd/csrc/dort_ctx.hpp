@@ -94,6 +94,8 @@ struct smrt_dort_ctx {
     struct MultiFresnelState* multifresnel = nullptr;
     // the iterative second-order solver (second_order.hip): likewise; its orders 0 and 1 are `first_order`'s
     struct SecondOrderState* second_order = nullptr;
+    // the nadir LRM altimetry solver (nadir_lrm_altimetry.hip): likewise
+    struct LrmState* lrm = nullptr;
 };
 
 #ifndef SMRT_JACOBI_NT
@@ -148,6 +150,8 @@ void successive_order_active_release(smrt_dort_ctx* ctx);
 void multifresnel_release(smrt_dort_ctx* ctx);
 // second_order.hip: frees ctx->second_order (smrt_dort_destroy)
 void second_order_release(smrt_dort_ctx* ctx);
+// nadir_lrm_altimetry.hip: frees ctx->lrm (smrt_dort_destroy)
+void lrm_release(smrt_dort_ctx* ctx);
 // first_order.hip: the resident batch of the first-order solver as its kernels get it (null: nothing uploaded); the
 // second-order solver sets its carry pointer and reads the staging rows and outputs
 smrt::FoBatch* first_order_resident(smrt_dort_ctx* ctx);

@@ -36,6 +36,8 @@ def ctype_of(decl):
         return "C.c_void_p"
     if base == "smrt_second_order_extras":   # {int32 interlayer, int32 reserved, int64 budget, two pointers}: likewise
         return "C.c_void_p"
+    if base == "smrt_lrm_params":   # the altimeter and options of one group (seven doubles, eight int32, four pointers): likewise
+        return "C.c_void_p"
     c = SCALARS[base]
     for _ in range(stars):
         c = "C.POINTER(%s)" % c
