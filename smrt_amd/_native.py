@@ -861,51 +861,84 @@ class DortContext:
                                                  _dptr(o.layers), _dptr(o.streams)), "smrt_dort_download")
         return o
 
-    # ---- the iterative first-order solver (smrt_first_order_*) ----------------------------------------------------
+    # ---- the solvers beside DORT: each has smrt_<prefix>_{run_pairs, upload_pairs, launch, sync, download, kernel_ms} ----
+    # A packer turns a public method's arguments into (the C arguments after the context, the arguments of the output
+    # class); the helpers below are what the public methods of every solver are made of.
+    def _solver_call(self, symbol, *args):
+        """One call into the library under the context's lock.  The convention of include/smrt_dort.h: negative means
+        error (a count or 0 is success)."""
+        with self.lock:
+            rc = getattr(self._lib, symbol)(self._h, *args)
+            if rc < 0:
+                raise SMRTError(f"{symbol} failed: {self._lib.smrt_dort_last_error(self._h).decode()}")
+        return rc
+
+    def _solver_run(self, prefix, output, cargs, oargs):
+        o = output(*oargs)
+        self._solver_call(f"smrt_{prefix}_run_pairs", *cargs, *o.pointers())
+        return o
+
+    def _solver_upload(self, prefix, cargs, oargs):
+        with self.lock:
+            self._solver_call(f"smrt_{prefix}_upload_pairs", *cargs)
+            setattr(self, f"_{prefix}_resident", oargs)
+
+    def _solver_download(self, prefix, output):
+        with self.lock:
+            o = output(*getattr(self, f"_{prefix}_resident"))
+            self._solver_call(f"smrt_{prefix}_download", *o.pointers())
+        return o
+
+    def _solver_kernel_ms(self, prefix, n):
+        a = np.zeros(n)
+        self._solver_call(f"smrt_{prefix}_kernel_ms", _dptr(a))
+        return tuple(float(x) for x in a)
+
+    def _solver_launch_info(self, prefix):
+        a = np.zeros(4, dtype=np.int64)
+        self._solver_call(f"smrt_{prefix}_launch_info", a.ctypes.data_as(C.POINTER(C.c_int64)), 4)   # (returns its number of entries)
+        return dict(chunks=int(a[0]), reserved_bytes=int(a[1]), over_budget=int(a[2]), budget=int(a[3]))
+
     @staticmethod
-    def _first_order_args(batch, extras, pairs):
-        if pairs is not None:
-            pairs = np.ascontiguousarray(pairs, dtype=np.int64)
-        return (C.byref(batch.struct), C.byref(extras.struct) if extras is not None else None,
-                pairs.ctypes.data_as(C.POINTER(C.c_int64)) if pairs is not None else None,
-                len(pairs) if pairs is not None else -1), pairs
+    def _pair_list(batch, pairs):
+        """(pointer, count, output rows) of an optional list of pair indices: (None, -1, every pair) without one."""
+        if pairs is None:
+            return None, -1, batch.n_pairs
+        pairs = np.ascontiguousarray(pairs, dtype=np.int64)
+        return pairs.ctypes.data_as(C.POINTER(C.c_int64)), len(pairs), len(pairs)
+
+    # ---- the iterative first-order solver (smrt_first_order_*) ----------------------------------------------------
+    @classmethod
+    def _first_order_pack(cls, batch, extras, pairs):
+        ptr, count, rows = cls._pair_list(batch, pairs)
+        return (C.byref(batch.struct), C.byref(extras.struct) if extras is not None else None, ptr, count), (batch, rows)
 
     def first_order_run(self, batch: PackedBatch, extras=None, pairs=None) -> FirstOrderOutput:
         """One shot (H2D, two kernels, D2H) for every pair of the batch or the listed ones (row i = pairs[i])."""
-        args, pairs = self._first_order_args(batch, extras, pairs)
-        o = FirstOrderOutput(batch, batch.n_pairs if pairs is None else len(pairs))
-        with self.lock:
-            self._check(self._lib.smrt_first_order_run_pairs(self._h, *args, *o.pointers()), "smrt_first_order_run_pairs")
-        return o
+        return self._solver_run("first_order", FirstOrderOutput, *self._first_order_pack(batch, extras, pairs))
 
     def first_order_upload(self, batch: PackedBatch, extras=None, pairs=None):
         """Split form (upload once, launch any number of times, sync, download).  Every call takes the context's lock,
         but the resident batch belongs to the context: a thread that uses the split form must hold `self.lock` from its
         upload to its download if another thread may solve on the same (cached) context meanwhile."""
-        args, pairs = self._first_order_args(batch, extras, pairs)
-        with self.lock:
-            self._check(self._lib.smrt_first_order_upload_pairs(self._h, *args), "smrt_first_order_upload_pairs")
-            self._first_order_resident = (batch, extras, pairs, batch.n_pairs if pairs is None else len(pairs))
+        self._solver_upload("first_order", *self._first_order_pack(batch, extras, pairs))
 
     def first_order_launch(self):
-        with self.lock:
-            self._check(self._lib.smrt_first_order_launch(self._h), "smrt_first_order_launch")
+        self._solver_call("smrt_first_order_launch")
 
     def first_order_sync(self):
-        with self.lock:
-            self._check(self._lib.smrt_first_order_sync(self._h), "smrt_first_order_sync")
+        self._solver_call("smrt_first_order_sync")
 
     def first_order_download(self, layers_only=False) -> FirstOrderOutput:
         """The outputs of the last launch; layers_only: only `layers` (and `status`) are copied back, the other arrays of
         the returned object are left unset."""
+        if not layers_only:
+            return self._solver_download("first_order", FirstOrderOutput)
         with self.lock:
-            batch, _, _, n = self._first_order_resident
-            o = FirstOrderOutput(batch, n)
+            o = FirstOrderOutput(*self._first_order_resident)
             ptrs = o.pointers()
-            if layers_only:
-                ptrs = (None, ptrs[1], ptrs[2], None, None)
-                o.values = o.layer_backscatter = o.diag = None
-            self._check(self._lib.smrt_first_order_download(self._h, *ptrs), "smrt_first_order_download")
+            o.values = o.layer_backscatter = o.diag = None
+            self._solver_call("smrt_first_order_download", None, ptrs[1], ptrs[2], None, None)
         return o
 
     def first_order_layers(self, batch: PackedBatch):
@@ -918,277 +951,174 @@ class DortContext:
 
     def first_order_kernel_ms(self):
         """HIP-event ms of the (pair, layer) kernel and of the (pair, angle) kernel of the last launch."""
-        a = np.zeros(2)
-        self._check(self._lib.smrt_first_order_kernel_ms(self._h, _dptr(a)), "smrt_first_order_kernel_ms")
-        return float(a[0]), float(a[1])
+        return self._solver_kernel_ms("first_order", 2)
 
     # ---- the iterative second-order solver (smrt_second_order_*): it replaces the resident first-order batch ----------
     def second_order_run(self, batch: PackedBatch, extras=None, pairs=None) -> SecondOrderOutput:
         """One shot (H2D, kernels, D2H) for every pair of the batch or the listed ones (row i = pairs[i])."""
-        args, pairs = self._first_order_args(batch, extras, pairs)
-        o = SecondOrderOutput(batch, batch.n_pairs if pairs is None else len(pairs))
-        with self.lock:
-            self._check(self._lib.smrt_second_order_run_pairs(self._h, *args, *o.pointers()), "smrt_second_order_run_pairs")
-        return o
+        return self._solver_run("second_order", SecondOrderOutput, *self._first_order_pack(batch, extras, pairs))
 
     def second_order_upload(self, batch: PackedBatch, extras=None, pairs=None):
         """Split form (upload once, launch any number of times, sync, download); see first_order_upload for the lock."""
-        args, pairs = self._first_order_args(batch, extras, pairs)
-        with self.lock:
-            self._check(self._lib.smrt_second_order_upload_pairs(self._h, *args), "smrt_second_order_upload_pairs")
-            self._second_order_resident = (batch, extras, pairs, batch.n_pairs if pairs is None else len(pairs))
+        self._solver_upload("second_order", *self._first_order_pack(batch, extras, pairs))
 
     def second_order_launch(self):
-        with self.lock:
-            self._check(self._lib.smrt_second_order_launch(self._h), "smrt_second_order_launch")
+        self._solver_call("smrt_second_order_launch")
 
     def second_order_sync(self):
-        with self.lock:
-            self._check(self._lib.smrt_second_order_sync(self._h), "smrt_second_order_sync")
+        self._solver_call("smrt_second_order_sync")
 
     def second_order_download(self) -> SecondOrderOutput:
-        with self.lock:
-            batch, _, _, n = self._second_order_resident
-            o = SecondOrderOutput(batch, n)
-            self._check(self._lib.smrt_second_order_download(self._h, *o.pointers()), "smrt_second_order_download")
-        return o
+        return self._solver_download("second_order", SecondOrderOutput)
 
     def second_order_kernel_ms(self):
         """HIP-event ms of the first-order kernels and of the order-2 kernels of the last launch."""
-        a = np.zeros(2)
-        self._check(self._lib.smrt_second_order_kernel_ms(self._h, _dptr(a)), "smrt_second_order_kernel_ms")
-        return float(a[0]), float(a[1])
+        return self._solver_kernel_ms("second_order", 2)
 
     # ---- the successive-order solver (smrt_successive_order_*) ----------------------------------------------------
-    @staticmethod
-    def _successive_order_args(batch, n_iteration_max, relative_tolerance, workspace_budget, pairs):
-        if pairs is not None:
-            pairs = np.ascontiguousarray(pairs, dtype=np.int64)
-        return (C.byref(batch.struct), int(n_iteration_max), float(relative_tolerance), int(workspace_budget or 0),
-                pairs.ctypes.data_as(C.POINTER(C.c_int64)) if pairs is not None else None,
-                len(pairs) if pairs is not None else -1), pairs
+    @classmethod
+    def _successive_order_pack(cls, batch, n_iteration_max, relative_tolerance, workspace_budget, pairs):
+        ptr, count, rows = cls._pair_list(batch, pairs)
+        return ((C.byref(batch.struct), int(n_iteration_max), float(relative_tolerance), int(workspace_budget or 0), ptr, count),
+                (batch, rows, int(n_iteration_max)))
 
     def successive_order_run(self, batch: PackedBatch, n_iteration_max=50, relative_tolerance=0.001, pairs=None,
                              workspace_budget=None) -> SuccessiveOrderOutput:
         """One shot (H2D, kernels chunk after chunk, D2H) for every pair of the batch or the listed ones (row i = pairs[i]).
         workspace_budget: bytes everything reserved on the device stays inside (None: the library's default)."""
-        args, pairs = self._successive_order_args(batch, n_iteration_max, relative_tolerance, workspace_budget, pairs)
-        o = SuccessiveOrderOutput(batch, batch.n_pairs if pairs is None else len(pairs), int(n_iteration_max))
-        with self.lock:
-            self._check(self._lib.smrt_successive_order_run_pairs(self._h, *args, *o.pointers()), "smrt_successive_order_run_pairs")
-        return o
+        return self._solver_run("successive_order", SuccessiveOrderOutput,
+                                *self._successive_order_pack(batch, n_iteration_max, relative_tolerance, workspace_budget, pairs))
 
     def successive_order_upload(self, batch: PackedBatch, n_iteration_max=50, relative_tolerance=0.001, pairs=None,
                                 workspace_budget=None):
         """Split form (upload once, launch any number of times, sync, download); see first_order_upload for the lock."""
-        args, pairs = self._successive_order_args(batch, n_iteration_max, relative_tolerance, workspace_budget, pairs)
-        with self.lock:
-            self._check(self._lib.smrt_successive_order_upload_pairs(self._h, *args), "smrt_successive_order_upload_pairs")
-            self._successive_order_resident = (batch, pairs, batch.n_pairs if pairs is None else len(pairs), int(n_iteration_max))
+        self._solver_upload("successive_order",
+                            *self._successive_order_pack(batch, n_iteration_max, relative_tolerance, workspace_budget, pairs))
 
     def successive_order_launch(self):
-        with self.lock:
-            self._check(self._lib.smrt_successive_order_launch(self._h), "smrt_successive_order_launch")
+        self._solver_call("smrt_successive_order_launch")
 
     def successive_order_sync(self):
-        with self.lock:
-            self._check(self._lib.smrt_successive_order_sync(self._h), "smrt_successive_order_sync")
+        self._solver_call("smrt_successive_order_sync")
 
     def successive_order_download(self) -> SuccessiveOrderOutput:
-        with self.lock:
-            batch, _, n, n_it = self._successive_order_resident
-            o = SuccessiveOrderOutput(batch, n, n_it)
-            self._check(self._lib.smrt_successive_order_download(self._h, *o.pointers()), "smrt_successive_order_download")
-        return o
+        return self._solver_download("successive_order", SuccessiveOrderOutput)
 
     def successive_order_kernel_ms(self):
         """HIP-event ms of the preparation kernels and of the sweep kernel of the last launch (summed over its chunks)."""
-        a = np.zeros(2)
-        with self.lock:
-            self._check(self._lib.smrt_successive_order_kernel_ms(self._h, _dptr(a)), "smrt_successive_order_kernel_ms")
-        return float(a[0]), float(a[1])
+        return self._solver_kernel_ms("successive_order", 2)
 
     def successive_order_launch_info(self):
         """dict(chunks, reserved_bytes, over_budget, budget) of the last launch."""
-        a = np.zeros(4, dtype=np.int64)
-        with self.lock:
-            # (returns the number of entries it has, -1 on error)
-            self._check(int(self._lib.smrt_successive_order_launch_info(self._h, a.ctypes.data_as(C.POINTER(C.c_int64)), 4) < 0),
-                        "smrt_successive_order_launch_info")
-        return dict(chunks=int(a[0]), reserved_bytes=int(a[1]), over_budget=int(a[2]), budget=int(a[3]))
+        return self._solver_launch_info("successive_order")
 
     # ---- the successive-order backscatter solver (smrt_so_active_*) -----------------------------------------------
-    @staticmethod
-    def _so_active_args(batch, n_iteration_max, relative_tolerance, theta_inc, incident_npol, m_max, workspace_budget, pairs):
-        if pairs is not None:
-            pairs = np.ascontiguousarray(pairs, dtype=np.int64)
+    @classmethod
+    def _so_active_pack(cls, batch, n_iteration_max, relative_tolerance, theta_inc, incident_npol, m_max, workspace_budget, pairs):
+        ptr, count, rows = cls._pair_list(batch, pairs)
         theta_inc = np.ascontiguousarray(np.atleast_1d(theta_inc), dtype=np.float64)
-        return (C.byref(batch.struct), int(n_iteration_max), float(relative_tolerance), len(theta_inc), _dptr(theta_inc),
-                int(incident_npol), int(m_max), int(workspace_budget or 0),
-                pairs.ctypes.data_as(C.POINTER(C.c_int64)) if pairs is not None else None,
-                len(pairs) if pairs is not None else -1), pairs, theta_inc
+        return ((C.byref(batch.struct), int(n_iteration_max), float(relative_tolerance), len(theta_inc), _dptr(theta_inc),
+                 int(incident_npol), int(m_max), int(workspace_budget or 0), ptr, count),
+                (batch, rows, int(n_iteration_max), len(theta_inc), int(m_max)))
 
     def so_active_run(self, batch: PackedBatch, theta_inc, n_iteration_max=50, relative_tolerance=0.001, incident_npol=2, m_max=2,
                       pairs=None, workspace_budget=None) -> SuccessiveOrderActiveOutput:
         """One shot (H2D, kernels chunk after chunk, D2H) for every pair of the (active) batch or the listed ones (row i =
         pairs[i]).  theta_inc: incidence angles (rad); workspace_budget: bytes everything reserved on the device stays inside."""
-        args, pairs, theta_inc = self._so_active_args(batch, n_iteration_max, relative_tolerance, theta_inc, incident_npol, m_max,
-                                                      workspace_budget, pairs)
-        o = SuccessiveOrderActiveOutput(batch, batch.n_pairs if pairs is None else len(pairs), int(n_iteration_max), len(theta_inc),
-                                        int(m_max))
-        with self.lock:
-            self._check(self._lib.smrt_so_active_run_pairs(self._h, *args, *o.pointers()), "smrt_so_active_run_pairs")
-        return o
+        return self._solver_run("so_active", SuccessiveOrderActiveOutput,
+                                *self._so_active_pack(batch, n_iteration_max, relative_tolerance, theta_inc, incident_npol, m_max,
+                                                      workspace_budget, pairs))
 
     def so_active_upload(self, batch: PackedBatch, theta_inc, n_iteration_max=50, relative_tolerance=0.001, incident_npol=2, m_max=2,
                          pairs=None, workspace_budget=None):
         """Split form (upload once, launch any number of times, sync, download); see first_order_upload for the lock."""
-        args, pairs, theta_inc = self._so_active_args(batch, n_iteration_max, relative_tolerance, theta_inc, incident_npol, m_max,
-                                                      workspace_budget, pairs)
-        with self.lock:
-            self._check(self._lib.smrt_so_active_upload_pairs(self._h, *args), "smrt_so_active_upload_pairs")
-            self._so_active_resident = (batch, pairs, batch.n_pairs if pairs is None else len(pairs), int(n_iteration_max),
-                                        len(theta_inc), int(m_max))
+        self._solver_upload("so_active", *self._so_active_pack(batch, n_iteration_max, relative_tolerance, theta_inc, incident_npol,
+                                                               m_max, workspace_budget, pairs))
 
     def so_active_launch(self):
-        with self.lock:
-            self._check(self._lib.smrt_so_active_launch(self._h), "smrt_so_active_launch")
+        self._solver_call("smrt_so_active_launch")
 
     def so_active_sync(self):
-        with self.lock:
-            self._check(self._lib.smrt_so_active_sync(self._h), "smrt_so_active_sync")
+        self._solver_call("smrt_so_active_sync")
 
     def so_active_download(self) -> SuccessiveOrderActiveOutput:
-        with self.lock:
-            batch, _, n, n_it, n_theta, m_max = self._so_active_resident
-            o = SuccessiveOrderActiveOutput(batch, n, n_it, n_theta, m_max)
-            self._check(self._lib.smrt_so_active_download(self._h, *o.pointers()), "smrt_so_active_download")
-        return o
+        return self._solver_download("so_active", SuccessiveOrderActiveOutput)
 
     def so_active_kernel_ms(self):
         """HIP-event ms of the preparation kernels, the sweep kernel and the combine kernel of the last launch."""
-        a = np.zeros(3)
-        with self.lock:
-            self._check(self._lib.smrt_so_active_kernel_ms(self._h, _dptr(a)), "smrt_so_active_kernel_ms")
-        return float(a[0]), float(a[1]), float(a[2])
+        return self._solver_kernel_ms("so_active", 3)
 
     def so_active_launch_info(self):
         """dict(chunks, reserved_bytes, over_budget, budget) of the last launch."""
-        a = np.zeros(4, dtype=np.int64)
-        with self.lock:
-            # (returns the number of entries it has, negative on error)
-            self._check(int(self._lib.smrt_so_active_launch_info(self._h, a.ctypes.data_as(C.POINTER(C.c_int64)), 4) < 0),
-                        "smrt_so_active_launch_info")
-        return dict(chunks=int(a[0]), reserved_bytes=int(a[1]), over_budget=int(a[2]), budget=int(a[3]))
+        return self._solver_launch_info("so_active")
 
     # ---- the multi-Fresnel thermal emission solver (smrt_multifresnel_*) -------------------------------------------
-    def _check_negative(self, rc, what):
-        """The convention of include/smrt_dort.h: negative means error (a count or 0 is success)."""
-        if rc < 0:
-            raise SMRTError(f"{what} failed: {self._lib.smrt_dort_last_error(self._h).decode()}")
-
-    @staticmethod
-    def _multifresnel_args(batch, mu, prune_deep_snowpack, pairs):
+    @classmethod
+    def _multifresnel_pack(cls, batch, mu, prune_deep_snowpack, pairs):
         mu = np.ascontiguousarray(np.atleast_1d(mu), dtype=np.float64)
         if len(mu) != int(batch.struct.n_theta):
             raise SMRTError("one sensor cosine per angle of the batch is needed")
-        if pairs is not None:
-            pairs = np.ascontiguousarray(pairs, dtype=np.int64)
+        ptr, count, rows = cls._pair_list(batch, pairs)
         none = prune_deep_snowpack is None
-        return (C.byref(batch.struct), _dptr(mu), 0.0 if none else float(prune_deep_snowpack), 1 if none else 0,
-                pairs.ctypes.data_as(C.POINTER(C.c_int64)) if pairs is not None else None,
-                len(pairs) if pairs is not None else -1), mu, pairs
+        return ((C.byref(batch.struct), _dptr(mu), 0.0 if none else float(prune_deep_snowpack), 1 if none else 0, ptr, count),
+                (batch, rows, mu))
 
     def multifresnel_run(self, batch: PackedBatch, mu, prune_deep_snowpack=10, pairs=None) -> MultiFresnelOutput:
         """One shot (H2D, two kernels, D2H) for every pair of the batch or the listed ones (row i = pairs[i]).  mu: the
         cosines of the sensor's angles; prune_deep_snowpack: an optical depth, or None for no pruning."""
-        args, mu, pairs = self._multifresnel_args(batch, mu, prune_deep_snowpack, pairs)
-        o = MultiFresnelOutput(batch, batch.n_pairs if pairs is None else len(pairs), mu)
-        with self.lock:
-            self._check_negative(self._lib.smrt_multifresnel_run_pairs(self._h, *args, *o.pointers()), "smrt_multifresnel_run_pairs")
-        return o
+        return self._solver_run("multifresnel", MultiFresnelOutput, *self._multifresnel_pack(batch, mu, prune_deep_snowpack, pairs))
 
     def multifresnel_upload(self, batch: PackedBatch, mu, prune_deep_snowpack=10, pairs=None):
         """Split form (upload once, launch any number of times, sync, download); see first_order_upload for the lock."""
-        args, mu, pairs = self._multifresnel_args(batch, mu, prune_deep_snowpack, pairs)
-        with self.lock:
-            self._check_negative(self._lib.smrt_multifresnel_upload_pairs(self._h, *args), "smrt_multifresnel_upload_pairs")
-            self._multifresnel_resident = (batch, mu, batch.n_pairs if pairs is None else len(pairs))
+        self._solver_upload("multifresnel", *self._multifresnel_pack(batch, mu, prune_deep_snowpack, pairs))
 
     def multifresnel_launch(self):
-        with self.lock:
-            self._check_negative(self._lib.smrt_multifresnel_launch(self._h), "smrt_multifresnel_launch")
+        self._solver_call("smrt_multifresnel_launch")
 
     def multifresnel_sync(self):
-        with self.lock:
-            self._check_negative(self._lib.smrt_multifresnel_sync(self._h), "smrt_multifresnel_sync")
+        self._solver_call("smrt_multifresnel_sync")
 
     def multifresnel_download(self) -> MultiFresnelOutput:
-        with self.lock:
-            batch, mu, n = self._multifresnel_resident
-            o = MultiFresnelOutput(batch, n, mu)
-            self._check_negative(self._lib.smrt_multifresnel_download(self._h, *o.pointers()), "smrt_multifresnel_download")
-        return o
+        return self._solver_download("multifresnel", MultiFresnelOutput)
 
     def multifresnel_kernel_ms(self):
         """HIP-event ms of the (pair, layer) kernel and of the (pair, angle) kernel of the last launch."""
-        a = np.zeros(2)
-        with self.lock:
-            self._check_negative(self._lib.smrt_multifresnel_kernel_ms(self._h, _dptr(a)), "smrt_multifresnel_kernel_ms")
-        return float(a[0]), float(a[1])
+        return self._solver_kernel_ms("multifresnel", 2)
 
     # ---- the nadir LRM altimetry solver (smrt_lrm_*) ----------------------------------------------------------------
-    @staticmethod
-    def _lrm_args(batch, params, pairs):
-        if pairs is not None:
-            pairs = np.ascontiguousarray(pairs, dtype=np.int64)
-        return (C.byref(batch.struct), C.byref(params.struct), pairs.ctypes.data_as(C.POINTER(C.c_int64)) if pairs is not None else None,
-                len(pairs) if pairs is not None else -1), pairs
+    @classmethod
+    def _lrm_pack(cls, batch, params, pairs):
+        ptr, count, rows = cls._pair_list(batch, pairs)
+        return (C.byref(batch.struct), C.byref(params.struct), ptr, count), (batch, params, rows)
 
     def lrm_run(self, batch: PackedBatch, params, pairs=None) -> LrmOutput:
         """One shot (H2D, three kernels, D2H) for every pair of the batch or the listed ones (row i = pairs[i])."""
-        args, pairs = self._lrm_args(batch, params, pairs)
-        o = LrmOutput(batch, params, batch.n_pairs if pairs is None else len(pairs))
-        with self.lock:
-            self._check_negative(self._lib.smrt_lrm_run_pairs(self._h, *args, *o.pointers()), "smrt_lrm_run_pairs")
-        return o
+        return self._solver_run("lrm", LrmOutput, *self._lrm_pack(batch, params, pairs))
 
     def lrm_upload(self, batch: PackedBatch, params, pairs=None):
         """Split form (upload once, launch any number of times, sync, download); see first_order_upload for the lock."""
-        args, pairs = self._lrm_args(batch, params, pairs)
-        with self.lock:
-            self._check_negative(self._lib.smrt_lrm_upload_pairs(self._h, *args), "smrt_lrm_upload_pairs")
-            self._lrm_resident = (batch, params, batch.n_pairs if pairs is None else len(pairs))
+        self._solver_upload("lrm", *self._lrm_pack(batch, params, pairs))
 
     def lrm_layers(self, batch: PackedBatch, params):
         """The layer scalars [n_pairs, Lmax, 5] of the batch alone: an upload and the (pair, layer) kernel, nothing else."""
         a = np.empty((batch.n_pairs, int(batch.struct.n_layers_max), 5))
         with self.lock:
             self.lrm_upload(batch, params)
-            self._check_negative(self._lib.smrt_lrm_layers(self._h, _dptr(a)), "smrt_lrm_layers")
+            self._solver_call("smrt_lrm_layers", _dptr(a))
         return a
 
     def lrm_launch(self):
-        with self.lock:
-            self._check_negative(self._lib.smrt_lrm_launch(self._h), "smrt_lrm_launch")
+        self._solver_call("smrt_lrm_launch")
 
     def lrm_sync(self):
-        with self.lock:
-            self._check_negative(self._lib.smrt_lrm_sync(self._h), "smrt_lrm_sync")
+        self._solver_call("smrt_lrm_sync")
 
     def lrm_download(self) -> LrmOutput:
-        with self.lock:
-            batch, params, n = self._lrm_resident
-            o = LrmOutput(batch, params, n)
-            self._check_negative(self._lib.smrt_lrm_download(self._h, *o.pointers()), "smrt_lrm_download")
-        return o
+        return self._solver_download("lrm", LrmOutput)
 
     def lrm_kernel_ms(self):
         """HIP-event ms of the three kernels of the last launch: layer scalars, vertical distribution, waveform."""
-        a = np.zeros(3)
-        with self.lock:
-            self._check_negative(self._lib.smrt_lrm_kernel_ms(self._h, _dptr(a)), "smrt_lrm_kernel_ms")
-        return tuple(float(x) for x in a)
+        return self._solver_kernel_ms("lrm", 3)
 
     def ft_even_phase(self, emmodel, microstructure, frequency, frac_volume, temperature, p1, p2, mu_s, mu_i, m_max, npol):
         """Azimuthal modes of the phase matrix of one layer: array [npol, npol, m_max + 1, len(mu_s), len(mu_i)]."""

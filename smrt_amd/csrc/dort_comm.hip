@@ -11,6 +11,7 @@
 #include "../../include/smrt_dort.h"
 #include "dort_ctx.hpp"
 #include "dort_host_common.hpp"
+#include "solver_host.hpp"   // HIPCHK
 
 namespace {
 
@@ -82,14 +83,6 @@ RcclApi& rccl() {
         ncclResult_t r_ = (call);                                                         \
         if (r_ != ncclSuccess) {                                                          \
             ctx->err = std::string(#call) + ": " + R.GetErrorString(r_);                  \
-            return -1;                                                                    \
-        }                                                                                 \
-    } while (0)
-#define HIPCHK(call)                                                                      \
-    do {                                                                                  \
-        hipError_t e_ = (call);                                                           \
-        if (e_ != hipSuccess) {                                                           \
-            ctx->err = std::string(#call) + ": " + hipGetErrorString(e_);                 \
             return -1;                                                                    \
         }                                                                                 \
     } while (0)

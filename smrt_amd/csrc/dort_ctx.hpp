@@ -84,17 +84,13 @@ struct smrt_dort_ctx {
     void* comm = nullptr;
     int comm_world = 0, comm_rank = 0;
     DevBuf d_gather_out, d_gather_status, d_scalar;
-    // the iterative first-order solver (first_order.hip): its own buffers and resident batch, made on first use
+    // the solvers beside DORT (first_order.hip, ..., nadir_lrm_altimetry.hip): each its own buffers and resident batch, made
+    // on first use (solver_host.hpp); orders 0 and 1 of the second-order solver are `first_order`'s
     struct FirstOrderState* first_order = nullptr;
-    // the successive-order solver (successive_order.hip): likewise
     struct SuccessiveOrderState* successive_order = nullptr;
-    // the successive-order backscatter solver (successive_order_active.hip): likewise
     struct SuccessiveOrderActiveState* successive_order_active = nullptr;
-    // the multi-Fresnel thermal emission solver (multifresnel.hip): likewise
     struct MultiFresnelState* multifresnel = nullptr;
-    // the iterative second-order solver (second_order.hip): likewise; its orders 0 and 1 are `first_order`'s
     struct SecondOrderState* second_order = nullptr;
-    // the nadir LRM altimetry solver (nadir_lrm_altimetry.hip): likewise
     struct LrmState* lrm = nullptr;
 };
 
@@ -140,17 +136,12 @@ hipError_t ft_even_phase(smrt_dort_ctx* ctx, const smrt::PhaseRequest& q);
 hipError_t prune_mark(smrt_dort_ctx* ctx, const smrt::DevBatch& c, int* done_dev);
 // k_cost.hip: sum of N_l^3 per pair from the stream counts alone
 hipError_t pair_cost(smrt_dort_ctx* ctx, const smrt::DevBatch& d, double* cost_dev);
-// first_order.hip: frees ctx->first_order (smrt_dort_destroy)
+// one per solver beside DORT, each in the solver's file: frees the solver's state on the context (smrt_dort_destroy)
 void first_order_release(smrt_dort_ctx* ctx);
-// successive_order.hip: frees ctx->successive_order (smrt_dort_destroy)
 void successive_order_release(smrt_dort_ctx* ctx);
-// successive_order_active.hip: frees ctx->successive_order_active (smrt_dort_destroy)
 void successive_order_active_release(smrt_dort_ctx* ctx);
-// multifresnel.hip: frees ctx->multifresnel (smrt_dort_destroy)
 void multifresnel_release(smrt_dort_ctx* ctx);
-// second_order.hip: frees ctx->second_order (smrt_dort_destroy)
 void second_order_release(smrt_dort_ctx* ctx);
-// nadir_lrm_altimetry.hip: frees ctx->lrm (smrt_dort_destroy)
 void lrm_release(smrt_dort_ctx* ctx);
 // first_order.hip: the resident batch of the first-order solver as its kernels get it (null: nothing uploaded); the
 // second-order solver sets its carry pointer and reads the staging rows and outputs

@@ -19,17 +19,9 @@
 #include "dort_phase_kernel.hpp"
 #include "dort_finish_reg.hpp"      // finish_reg_lds_doubles (device code is inline templates / functions: nothing is instantiated here)
 #include "dort_finish_strip.hpp"    // finish_strip_lds_doubles
+#include "solver_host.hpp"          // HIPCHK
 
 using namespace smrt;
-
-#define HIPCHK(call)                                                                              \
-    do {                                                                                          \
-        hipError_t e_ = (call);                                                                   \
-        if (e_ != hipSuccess) {                                                                   \
-            ctx->err = std::string(#call) + ": " + hipGetErrorString(e_);                         \
-            return -1;                                                                            \
-        }                                                                                         \
-    } while (0)
 
 static int upload_array(smrt_dort_ctx* ctx, DevBuf& buf, const void* src, size_t bytes) {
     HIPCHK(buf.reserve(bytes));

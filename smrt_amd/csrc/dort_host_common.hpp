@@ -165,4 +165,71 @@ inline const char* validate(const smrt_batch* b) {
     return nullptr;
 }
 
+// What the solvers beside DORT refuse alike (solver_refusals.hpp holds each solver's own checks, and calls these between
+// them in the order its refusals have always had).  What a solver accepts of the batch:
+struct SolverAccepts {
+    bool theta;                      // b->theta is read: null is refused
+    bool layer_emmodels;             // false: emmodel codes are not looked at (every one evaluates, or the solver checks them itself)
+    unsigned emmodel_refused;        // bit e: emmodel code e (of the batch, or of a layer_kind entry) is refused ...
+    const char* emmodel_refusal;     // ... with this message
+    const char* dmrt_refusal;        // not null: refuses the DMRT short-range emmodels (after their microstructure check)
+    int substrate_last;              // substrate kinds SMRT_SUBSTRATE_NONE .. substrate_last are taken ...
+    const char* substrate_refusal;   // ... the others refused with this message
+    bool substrate_temperature;      // a substrate needs substrate_temperature too
+};
+constexpr unsigned kHostEmmodels = 1u << SMRT_EM_HOST | 1u << SMRT_EM_IBA_HOST | 1u << SMRT_EM_RAYLEIGH_HOST;
+
+inline const char* refuse_empty(const smrt_batch* b) {
+    if (!b) return "null batch";
+    if (b->n_snowpacks <= 0 || b->n_frequencies <= 0 || b->n_layers_max <= 0) return "empty batch";
+    return nullptr;
+}
+
+inline const char* refuse_emmodel(int em, int ms, const SolverAccepts& a) {
+    if (a.emmodel_refused >> em & 1) return a.emmodel_refusal;
+    if (em == SMRT_EM_DMRT_QCA_SHORTRANGE || em == SMRT_EM_DMRT_QCACP_SHORTRANGE) {
+        if (ms != SMRT_MS_STICKY_HARD_SPHERES) return "the dmrt short-range emmodels are only compatible with sticky_hard_spheres";
+        return a.dmrt_refusal;
+    }
+    return nullptr;
+}
+
+// the model codes, the input arrays, n_layers and the layer_kind entries (a non-empty batch)
+inline const char* refuse_inputs(const smrt_batch* b, const SolverAccepts& a) {
+    if (b->emmodel < SMRT_EM_IBA || b->emmodel > SMRT_EM_RAYLEIGH_HOST) return "unknown emmodel";
+    if (b->microstructure < SMRT_MS_EXPONENTIAL || b->microstructure > SMRT_MS_TEUBNER_STREY) return "unknown microstructure";
+    if (!b->n_layers || !b->thickness || !b->frac_volume || !b->temperature || !b->micro_p1 || !b->frequency || (a.theta && !b->theta))
+        return "null input array";
+    if ((b->microstructure == SMRT_MS_STICKY_HARD_SPHERES || b->layer_kind) && !b->micro_p2) return "stickiness array missing";
+    const char* why = (a.layer_emmodels && !b->layer_kind) ? refuse_emmodel(b->emmodel, b->microstructure, a) : nullptr;
+    if (why) return why;
+    for (int s = 0; s < b->n_snowpacks; ++s) {
+        if (b->n_layers[s] < 1 || b->n_layers[s] > b->n_layers_max) return "n_layers out of range";
+        for (int l = 0; b->layer_kind && l < b->n_layers[s]; ++l) {
+            const int k = b->layer_kind[(long long)s * b->n_layers_max + l], em = k & 15, ms = k >> 4;
+            if (ms < SMRT_MS_EXPONENTIAL || ms > SMRT_MS_TEUBNER_STREY) return "invalid layer_kind entry";
+            if (!a.layer_emmodels) continue;
+            if (em > SMRT_EM_RAYLEIGH_HOST && !(a.emmodel_refused >> em & 1)) return "invalid layer_kind entry";
+            if ((why = refuse_emmodel(em, ms, a))) return why;
+        }
+    }
+    return nullptr;
+}
+
+inline const char* refuse_substrate(const smrt_batch* b, const SolverAccepts& a) {
+    if (b->substrate_kind < SMRT_SUBSTRATE_NONE || b->substrate_kind > a.substrate_last) return a.substrate_refusal;
+    if (b->substrate_kind != SMRT_SUBSTRATE_NONE && (!b->substrate_p1 || !b->substrate_p2 || (a.substrate_temperature && !b->substrate_temperature)))
+        return "substrate arrays missing";
+    return nullptr;
+}
+
+// The pair list of an *_upload_pairs call: null means all `all` pairs (*n_pairs is set), otherwise every index must be one.
+inline const char* refuse_pairs(const int64_t* pairs, int64_t* n_pairs, int64_t all) {
+    if (!pairs) { *n_pairs = all; return nullptr; }
+    if (*n_pairs <= 0) return "empty pair list";
+    for (int64_t i = 0; i < *n_pairs; ++i)
+        if (pairs[i] < 0 || pairs[i] >= all) return "pair index out of bounds";
+    return nullptr;
+}
+
 }  // namespace smrt_host

@@ -7,20 +7,11 @@
 #include <cstring>
 #include <string>
 
-#include "dort_ctx.hpp"
 #include "first_order_kernel.hpp"
-#include "../../include/smrt_dort.h"
+#include "solver_host.hpp"
+#include "solver_refusals.hpp"
 
 using namespace smrt;
-
-#define HIPCHK(call)                                                                              \
-    do {                                                                                          \
-        hipError_t e_ = (call);                                                                   \
-        if (e_ != hipSuccess) {                                                                   \
-            ctx->err = std::string(#call) + ": " + hipGetErrorString(e_);                         \
-            return -1;                                                                            \
-        }                                                                                         \
-    } while (0)
 
 constexpr int kFoThreads = 256;
 
@@ -36,79 +27,21 @@ __global__ void __launch_bounds__(kFoThreads) first_order_angles_kernel(FoBatch 
     first_order_angle_item(b, idx / b.n_theta, (int)(idx % b.n_theta));   // angles fastest: a wavefront reads 64 / n_theta consecutive staging entries and writes whole output rows
 }
 
-struct FirstOrderState {
-    DevBuf nl, thick, fv, temp, p1, p2, freq, theta, lw, kind, hostlayer, hostcoeff, sub1, sub2, pairmap, slot, values, phase;
-    DevBuf stage, out, status, layer, lb, diag;
+struct FirstOrderState : solver_host::InputState {
+    DevBuf &theta = buf(), &hostlayer = buf(), &hostcoeff = buf(), &slot = buf(), &values = buf(), &phase = buf();
+    DevBuf &stage = buf(), &out = buf(), &status = buf(), &layer = buf(), &lb = buf(), &diag = buf();
     FoBatch dev{};
     bool uploaded = false;
-    hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
-    bool timed = false;
+    bool timed = false;   // events 0, 1, 2 around the two kernels of the last launch
 };
 
 namespace smrt_launch {
-void first_order_release(smrt_dort_ctx* ctx) {
-    FirstOrderState* st = ctx->first_order;
-    if (!st) return;
-    DevBuf* bufs[] = {&st->nl, &st->thick, &st->fv, &st->temp, &st->p1, &st->p2, &st->freq, &st->theta, &st->lw, &st->kind,
-                      &st->hostlayer, &st->hostcoeff, &st->sub1, &st->sub2, &st->pairmap, &st->slot, &st->values, &st->phase,
-                      &st->stage, &st->out, &st->status, &st->layer, &st->lb, &st->diag};
-    for (DevBuf* b : bufs) b->release();
-    for (hipEvent_t e : st->ev) if (e) (void)hipEventDestroy(e);
-    delete st;
-    ctx->first_order = nullptr;
-}
+void first_order_release(smrt_dort_ctx* ctx) { solver_host::release(ctx->first_order); }
 FoBatch* first_order_resident(smrt_dort_ctx* ctx) {
     FirstOrderState* st = ctx->first_order;
     return st && st->uploaded ? &st->dev : nullptr;
 }
 }  // namespace smrt_launch
-
-static int fo_upload(smrt_dort_ctx* ctx, DevBuf& buf, const void* src, size_t bytes) {
-    HIPCHK(buf.reserve(bytes));
-    HIPCHK(hipMemcpyAsync(buf.p, src, bytes, hipMemcpyHostToDevice, ctx->stream));
-    return 0;
-}
-
-static const char* fo_validate(const smrt_batch* b, const smrt_first_order_extras* x) {
-    if (!b) return "null batch";
-    if (b->n_snowpacks <= 0 || b->n_frequencies <= 0 || b->n_layers_max <= 0) return "empty batch";
-    if (b->n_theta <= 0) return "n_theta must be positive";
-    if (b->mode != SMRT_MODE_ACTIVE) return "the iterative first-order solver needs an active sensor";
-    if (b->emmodel < SMRT_EM_IBA || b->emmodel > SMRT_EM_RAYLEIGH_HOST) return "unknown emmodel";
-    if (b->microstructure < SMRT_MS_EXPONENTIAL || b->microstructure > SMRT_MS_TEUBNER_STREY) return "unknown microstructure";
-    if (!b->n_layers || !b->thickness || !b->frac_volume || !b->temperature || !b->micro_p1 || !b->frequency || !b->theta)
-        return "null input array";
-    if ((b->microstructure == SMRT_MS_STICKY_HARD_SPHERES || b->layer_kind) && !b->micro_p2) return "stickiness array missing";
-    bool host_scalars = !b->layer_kind && b->emmodel >= SMRT_EM_HOST && b->emmodel != SMRT_EM_IBA_INVERTED;
-    bool iba_host = !b->layer_kind && b->emmodel == SMRT_EM_IBA_HOST;
-    bool dmrt = !b->layer_kind && (b->emmodel == SMRT_EM_DMRT_QCA_SHORTRANGE || b->emmodel == SMRT_EM_DMRT_QCACP_SHORTRANGE);
-    if (dmrt && b->microstructure != SMRT_MS_STICKY_HARD_SPHERES)
-        return "the dmrt short-range emmodels are only compatible with sticky_hard_spheres";
-    for (int s = 0; s < b->n_snowpacks; ++s) {
-        if (b->n_layers[s] < 1 || b->n_layers[s] > b->n_layers_max) return "n_layers out of range";
-        for (int l = 0; b->layer_kind && l < b->n_layers[s]; ++l) {
-            const int k = b->layer_kind[(long long)s * b->n_layers_max + l], em = k & 15, ms = k >> 4;
-            if (em < SMRT_EM_IBA || em > SMRT_EM_RAYLEIGH_HOST || ms < SMRT_MS_EXPONENTIAL || ms > SMRT_MS_TEUBNER_STREY)
-                return "invalid layer_kind entry";
-            if ((em == SMRT_EM_DMRT_QCA_SHORTRANGE || em == SMRT_EM_DMRT_QCACP_SHORTRANGE) && ms != SMRT_MS_STICKY_HARD_SPHERES)
-                return "the dmrt short-range emmodels are only compatible with sticky_hard_spheres";
-            if (em == SMRT_EM_HOST || em == SMRT_EM_IBA_HOST || em == SMRT_EM_RAYLEIGH_HOST) host_scalars = true;
-            if (em == SMRT_EM_IBA_HOST) iba_host = true;
-        }
-    }
-    if (host_scalars && !b->host_layer) return "layers evaluated by the caller need host_layer";
-    if (iba_host && !b->host_iba_coeff) return "layers of kind SMRT_EM_IBA_HOST need host_iba_coeff";
-    if (b->substrate_kind < SMRT_SUBSTRATE_NONE || b->substrate_kind > SMRT_SUBSTRATE_REFLECTOR)
-        return "substrate_kind must be none, flat or reflector: any other substrate travels in smrt_first_order_extras";
-    if (b->substrate_kind != SMRT_SUBSTRATE_NONE && (!b->substrate_p1 || !b->substrate_p2)) return "substrate arrays missing";
-    if (x && x->host_interface_slot) {
-        if (x->n_interface_slots < 1 || !x->host_interface_values) return "host_interface_slot needs host_interface_values and n_interface_slots >= 1";
-        const long long n = (long long)b->n_frequencies * b->n_snowpacks * (b->n_layers_max + 1);
-        for (long long i = 0; i < n; ++i)
-            if (x->host_interface_slot[i] < -1 || x->host_interface_slot[i] >= x->n_interface_slots) return "host_interface_slot entry out of range";
-    }
-    return nullptr;
-}
 
 extern "C" {
 
@@ -119,61 +52,37 @@ int32_t smrt_first_order_abi(int32_t* out, int32_t capacity) {
     const int32_t desc[] = {(int32_t)sizeof(smrt_first_order_extras), SMRT_OFF(n_interface_slots), SMRT_OFF(reserved),
                             SMRT_OFF(host_interface_slot), SMRT_OFF(host_interface_values), SMRT_OFF(host_phase_samples)};
 #undef SMRT_OFF
-    const int32_t n = (int32_t)(sizeof(desc) / sizeof(desc[0]));
-    for (int32_t i = 0; out && i < n && i < capacity; ++i) out[i] = desc[i];
-    return n;
+    return solver_host::copy_table(desc, out, capacity);
 }
 
 int32_t smrt_first_order_upload_pairs(smrt_dort_ctx* ctx, const smrt_batch* b, const smrt_first_order_extras* x,
                                       const int64_t* pairs, int64_t n_pairs) {
     if (!ctx) return -1;
-    const char* why = fo_validate(b, x);
+    const char* why = solver_refusals::first_order(b, x);
     if (why) { ctx->err = why; return -1; }
-    const int64_t all = (int64_t)b->n_snowpacks * b->n_frequencies;
-    if (!pairs) n_pairs = all;
-    else {
-        if (n_pairs <= 0) { ctx->err = "empty pair list"; return -1; }
-        for (int64_t i = 0; i < n_pairs; ++i)
-            if (pairs[i] < 0 || pairs[i] >= all) { ctx->err = "pair index out of bounds"; return -1; }
-    }
+    if (solver_host::check_pairs(ctx, pairs, &n_pairs, (int64_t)b->n_snowpacks * b->n_frequencies)) return -1;
     HIPCHK(hipSetDevice(ctx->device));
-    if (!ctx->first_order) {
-        ctx->first_order = new FirstOrderState();
-        for (hipEvent_t& e : ctx->first_order->ev) HIPCHK(hipEventCreate(&e));
-    }
+    if (!ctx->first_order) ctx->first_order = new FirstOrderState();
     FirstOrderState* st = ctx->first_order;
     st->uploaded = false;
     const size_t S = b->n_snowpacks, L = b->n_layers_max, F = b->n_frequencies, T = b->n_theta, N = (size_t)n_pairs;
-    const size_t SL = S * L * sizeof(double), FS = F * S;
+    const size_t FS = F * S;
     FoBatch d{};
     d.S = (int)S; d.Lmax = (int)L; d.F = (int)F; d.n_theta = (int)T;
     d.emmodel = b->emmodel; d.micro = b->microstructure; d.sub_kind = b->substrate_kind;
     d.n_pairs = n_pairs;
-#define FO_UP(buf, src, bytes, field) do { if (fo_upload(ctx, st->buf, src, bytes)) return -1; d.field = (decltype(d.field))st->buf.p; } while (0)
-    FO_UP(nl, b->n_layers, S * sizeof(int32_t), n_layers);
-    FO_UP(thick, b->thickness, SL, thickness);
-    FO_UP(fv, b->frac_volume, SL, frac_volume);
-    FO_UP(temp, b->temperature, SL, temperature);
-    FO_UP(p1, b->micro_p1, SL, p1);
-    if (b->micro_p2) FO_UP(p2, b->micro_p2, SL, p2);
-    FO_UP(freq, b->frequency, F * sizeof(double), frequency);
-    FO_UP(theta, b->theta, T * sizeof(double), theta);
-    if (b->liquid_water) FO_UP(lw, b->liquid_water, SL, liquid_water);
-    if (b->layer_kind) FO_UP(kind, b->layer_kind, S * L * sizeof(int32_t), layer_kind);
-    if (b->host_layer) FO_UP(hostlayer, b->host_layer, FS * L * 4 * sizeof(double), host_layer);
-    if (b->host_iba_coeff) FO_UP(hostcoeff, b->host_iba_coeff, FS * L * sizeof(double), host_coeff);
-    if (b->substrate_kind != SMRT_SUBSTRATE_NONE) {
-        FO_UP(sub1, b->substrate_p1, FS * sizeof(double), sub_p1);
-        FO_UP(sub2, b->substrate_p2, FS * sizeof(double), sub_p2);
-    }
-    if (pairs) FO_UP(pairmap, pairs, N * sizeof(int64_t), pair_map);
+    using solver_host::upload;
+    if (solver_host::upload_batch(ctx, st, b, pairs, d)) return -1;
+    if (upload(ctx, st->theta, b->theta, T * sizeof(double), d.theta)) return -1;
+    if (b->host_layer && upload(ctx, st->hostlayer, b->host_layer, FS * L * 4 * sizeof(double), d.host_layer)) return -1;
+    if (b->host_iba_coeff && upload(ctx, st->hostcoeff, b->host_iba_coeff, FS * L * sizeof(double), d.host_coeff)) return -1;
     if (x && x->host_interface_slot) {
         d.n_slots = x->n_interface_slots;
-        FO_UP(slot, x->host_interface_slot, FS * (L + 1) * sizeof(int32_t), itf_slot);
-        FO_UP(values, x->host_interface_values, FS * (size_t)d.n_slots * T * kFoInterfaceDoubles * sizeof(double), itf_values);
+        if (upload(ctx, st->slot, x->host_interface_slot, FS * (L + 1) * sizeof(int32_t), d.itf_slot) ||
+            upload(ctx, st->values, x->host_interface_values, FS * (size_t)d.n_slots * T * kFoInterfaceDoubles * sizeof(double), d.itf_values))
+            return -1;
     }
-    if (x && x->host_phase_samples) FO_UP(phase, x->host_phase_samples, FS * L * T * 16 * sizeof(double), host_phase);
-#undef FO_UP
+    if (x && x->host_phase_samples && upload(ctx, st->phase, x->host_phase_samples, FS * L * T * 16 * sizeof(double), d.host_phase)) return -1;
     HIPCHK(st->stage.reserve((size_t)FO_ROWS * L * N * sizeof(double)));
     HIPCHK(st->out.reserve(N * 16 * T * sizeof(double)));
     HIPCHK(st->status.reserve(N * sizeof(int32_t)));
@@ -182,8 +91,7 @@ int32_t smrt_first_order_upload_pairs(smrt_dort_ctx* ctx, const smrt_batch* b, c
     HIPCHK(st->diag.reserve(N * 2 * sizeof(double)));
     d.stage = (double*)st->stage.p; d.out = (double*)st->out.p; d.status = (int*)st->status.p;
     d.layer_out = (double*)st->layer.p; d.layer_backscatter = (double*)st->lb.p; d.diag = (double*)st->diag.p;
-    // the copies above read the caller's (pageable) arrays: wait for them, the arrays may go away or change after this call
-    HIPCHK(hipStreamSynchronize(ctx->stream));
+    if (solver_host::uploads_done(ctx)) return -1;
     st->dev = d;
     st->uploaded = true;
     st->timed = false;
@@ -197,36 +105,28 @@ int32_t smrt_first_order_launch(smrt_dort_ctx* ctx) {
     HIPCHK(hipSetDevice(ctx->device));
     const FoBatch& d = st->dev;
     const long long items_a = d.n_pairs * d.Lmax, items_b = d.n_pairs * d.n_theta;
-    HIPCHK(hipEventRecord(st->ev[0], ctx->stream));
+    st->rewind();
+    if (solver_host::record(ctx, st)) return -1;
     hipLaunchKernelGGL(first_order_layers_kernel, dim3((unsigned)((items_a + kFoThreads - 1) / kFoThreads)), dim3(kFoThreads), 0,
                        ctx->stream, d);
     HIPCHK(hipGetLastError());
-    HIPCHK(hipEventRecord(st->ev[1], ctx->stream));
+    if (solver_host::record(ctx, st)) return -1;
     hipLaunchKernelGGL(first_order_angles_kernel, dim3((unsigned)((items_b + kFoThreads - 1) / kFoThreads)), dim3(kFoThreads), 0,
                        ctx->stream, d);
     HIPCHK(hipGetLastError());
-    HIPCHK(hipEventRecord(st->ev[2], ctx->stream));
+    if (solver_host::record(ctx, st)) return -1;
     st->timed = true;
     return 0;
 }
 
-int32_t smrt_first_order_sync(smrt_dort_ctx* ctx) {
-    if (!ctx) return -1;
-    HIPCHK(hipSetDevice(ctx->device));
-    HIPCHK(hipStreamSynchronize(ctx->stream));
-    return 0;
-}
+int32_t smrt_first_order_sync(smrt_dort_ctx* ctx) { return solver_host::sync(ctx); }
 
 int32_t smrt_first_order_kernel_ms(smrt_dort_ctx* ctx, double* ms2) {
     if (!ctx || !ms2) return -1;
     FirstOrderState* st = ctx->first_order;
     if (!st || !st->timed) { ctx->err = "no first-order launch to time"; return -1; }
-    HIPCHK(hipSetDevice(ctx->device));
-    HIPCHK(hipEventSynchronize(st->ev[2]));
-    float a = 0.f, c = 0.f;
-    HIPCHK(hipEventElapsedTime(&a, st->ev[0], st->ev[1]));
-    HIPCHK(hipEventElapsedTime(&c, st->ev[1], st->ev[2]));
-    ms2[0] = a; ms2[1] = c;
+    ms2[0] = ms2[1] = 0.0;
+    if (solver_host::wait_recorded(ctx, st) || solver_host::add_elapsed(ctx, st, 0, 1, &ms2[0]) || solver_host::add_elapsed(ctx, st, 1, 2, &ms2[1])) return -1;
     return 0;
 }
 

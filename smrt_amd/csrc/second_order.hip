@@ -10,21 +10,11 @@
 #include <string>
 #include <vector>
 
-#include "dort_ctx.hpp"
-#include "dort_host_common.hpp"
 #include "second_order_kernel.hpp"
-#include "../../include/smrt_dort.h"
+#include "solver_host.hpp"
+#include "solver_refusals.hpp"
 
 using namespace smrt;
-
-#define HIPCHK(call)                                                                              \
-    do {                                                                                          \
-        hipError_t e_ = (call);                                                                   \
-        if (e_ != hipSuccess) {                                                                   \
-            ctx->err = std::string(#call) + ": " + hipGetErrorString(e_);                         \
-            return -1;                                                                            \
-        }                                                                                         \
-    } while (0)
 
 constexpr int kSo2Threads = 256;                       // four wavefronts = four integral units per workgroup
 constexpr int kSo2UnitsPerBlock = kSo2Threads / SMRT_LANES;
@@ -57,37 +47,16 @@ __global__ void __launch_bounds__(kSo2Threads) second_order_walk_kernel(So2Batch
     second_order_walk_item(b, idx / b.fo.n_theta, (int)(idx % b.fo.n_theta));
 }
 
-struct SecondOrderState {
-    DevBuf gl, submodes, carry, out, lb, nstream, streams, integ;
+struct SecondOrderState : solver_host::SolverState {
+    DevBuf &gl = buf(), &submodes = buf(), &carry = buf(), &out = buf(), &lb = buf(), &nstream = buf(), &streams = buf(), &integ = buf();
     So2Batch dev{};
     long long chunk_rows = 0;
-    bool uploaded = false, timed = false;
-    hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
+    bool uploaded = false, timed = false;   // events 0, 1, 2 around the first-order launch and the chunks of the last launch
 };
 
 namespace smrt_launch {
-void second_order_release(smrt_dort_ctx* ctx) {
-    SecondOrderState* st = ctx->second_order;
-    if (!st) return;
-    DevBuf* bufs[] = {&st->gl, &st->submodes, &st->carry, &st->out, &st->lb, &st->nstream, &st->streams, &st->integ};
-    for (DevBuf* b : bufs) b->release();
-    for (hipEvent_t e : st->ev) if (e) (void)hipEventDestroy(e);
-    delete st;
-    ctx->second_order = nullptr;
-}
+void second_order_release(smrt_dort_ctx* ctx) { solver_host::release(ctx->second_order); }
 }  // namespace smrt_launch
-
-static const char* so2_validate(const smrt_batch* b) {
-    if (!b) return "null batch";
-    if (b->n_max_stream < 2 || b->n_max_stream > 1024) return "n_max_stream must be 2 to 1024";
-    if (b->m_max < 1 || b->m_max > kSo2MaxModes) return "m_max must be 1 to 8";
-    if (!b->layer_kind && b->emmodel == SMRT_EM_HOST) return "the iterative second-order solver has no route for emmodels evaluated by the caller (SMRT_EM_HOST)";
-    for (int s = 0; b->layer_kind && b->n_layers && s < b->n_snowpacks; ++s)
-        for (int l = 0; l < b->n_layers[s] && l < b->n_layers_max; ++l)
-            if ((b->layer_kind[(long long)s * b->n_layers_max + l] & 15) == SMRT_EM_HOST)
-                return "the iterative second-order solver has no route for emmodels evaluated by the caller (SMRT_EM_HOST)";
-    return nullptr;
-}
 
 template <int M>
 static void so2_launch_integrals(const So2Batch& d, hipStream_t stream) {
@@ -110,23 +79,18 @@ int32_t smrt_second_order_abi(int32_t* out, int32_t capacity) {
     const int32_t desc[] = {(int32_t)sizeof(smrt_second_order_extras), SMRT_OFF(compute_scattering_interlayer), SMRT_OFF(reserved),
                             SMRT_OFF(workspace_budget_bytes), SMRT_OFF(first_order), SMRT_OFF(substrate_diffuse_modes)};
 #undef SMRT_OFF
-    const int32_t n = (int32_t)(sizeof(desc) / sizeof(desc[0]));
-    for (int32_t i = 0; out && i < n && i < capacity; ++i) out[i] = desc[i];
-    return n;
+    return solver_host::copy_table(desc, out, capacity);
 }
 
 int32_t smrt_second_order_upload_pairs(smrt_dort_ctx* ctx, const smrt_batch* b, const smrt_second_order_extras* x,
                                        const int64_t* pairs, int64_t n_pairs) {
     if (!ctx) return -1;
-    const char* why = so2_validate(b);
+    const char* why = solver_refusals::second_order(b);
     if (why) { ctx->err = why; return -1; }
     if (ctx->second_order) ctx->second_order->uploaded = false;
     // inputs, staging rows and first-order outputs: the first-order solver's own upload (it validates the rest)
     if (smrt_first_order_upload_pairs(ctx, b, x ? x->first_order : nullptr, pairs, n_pairs)) return -1;
-    if (!ctx->second_order) {
-        ctx->second_order = new SecondOrderState();
-        for (hipEvent_t& e : ctx->second_order->ev) HIPCHK(hipEventCreate(&e));
-    }
+    if (!ctx->second_order) ctx->second_order = new SecondOrderState();
     SecondOrderState* st = ctx->second_order;
     FoBatch* fo = smrt_launch::first_order_resident(ctx);
     if (!fo) { ctx->err = "no first-order batch resident"; return -1; }
@@ -148,13 +112,8 @@ int32_t smrt_second_order_upload_pairs(smrt_dort_ctx* ctx, const smrt_batch* b, 
     st->chunk_rows = (long long)std::min<size_t>(N, (size_t)(budget - (int64_t)fixed) / per_row);
     std::vector<double> gl(NM);
     smrt_host::gauss_legendre_positive((int)NM, gl.data(), nullptr);
-    HIPCHK(st->gl.reserve(NM * sizeof(double)));
-    HIPCHK(hipMemcpyAsync(st->gl.p, gl.data(), NM * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-    if (sub_bytes) {
-        HIPCHK(st->submodes.reserve(sub_bytes));
-        HIPCHK(hipMemcpyAsync(st->submodes.p, x->substrate_diffuse_modes, sub_bytes, hipMemcpyHostToDevice, ctx->stream));
-        d.sub_modes = (const double*)st->submodes.p;
-    }
+    if (solver_host::upload(ctx, st->gl, gl.data(), NM * sizeof(double), d.gl_mu)) return -1;
+    if (sub_bytes && solver_host::upload(ctx, st->submodes, x->substrate_diffuse_modes, sub_bytes, d.sub_modes)) return -1;
     HIPCHK(st->carry.reserve(N * L * T * kFoCarryDoubles * sizeof(double)));
     HIPCHK(st->out.reserve(N * 28 * T * sizeof(double)));
     HIPCHK(st->lb.reserve(N * (L + 1) * T * 4 * sizeof(double)));
@@ -162,10 +121,9 @@ int32_t smrt_second_order_upload_pairs(smrt_dort_ctx* ctx, const smrt_batch* b, 
     HIPCHK(st->nstream.reserve(R * L * sizeof(int32_t)));
     HIPCHK(st->streams.reserve(R * L * 2 * NM * sizeof(double)));
     HIPCHK(st->integ.reserve(R * L * T * slots * 4 * sizeof(double)));
-    HIPCHK(hipStreamSynchronize(ctx->stream));   // gl is this function's own vector; the caller's modes may go away
+    if (solver_host::uploads_done(ctx)) return -1;
     fo->carry = (double*)st->carry.p;
     d.fo = *fo;
-    d.gl_mu = (const double*)st->gl.p;
     d.nstream = (int*)st->nstream.p; d.streams = (double*)st->streams.p; d.integ = (double*)st->integ.p;
     d.out = (double*)st->out.p; d.layer_backscatter = (double*)st->lb.p;
     st->dev = d;
@@ -183,9 +141,10 @@ int32_t smrt_second_order_launch(smrt_dort_ctx* ctx) {
         return -1;
     }
     HIPCHK(hipSetDevice(ctx->device));
-    HIPCHK(hipEventRecord(st->ev[0], ctx->stream));
+    st->rewind();
+    if (solver_host::record(ctx, st)) return -1;
     if (smrt_first_order_launch(ctx)) return -1;   // layer scalars, orders 0 and 1, the carry
-    HIPCHK(hipEventRecord(st->ev[1], ctx->stream));
+    if (solver_host::record(ctx, st)) return -1;
     So2Batch d = st->dev;
     const long long N = d.fo.n_pairs, L = d.fo.Lmax, T = d.fo.n_theta;
     for (long long begin = 0; begin < N; begin += st->chunk_rows) {
@@ -203,23 +162,19 @@ int32_t smrt_second_order_launch(smrt_dort_ctx* ctx) {
                            dim3(kSo2Threads), 0, ctx->stream, d);
         HIPCHK(hipGetLastError());
     }
-    HIPCHK(hipEventRecord(st->ev[2], ctx->stream));
+    if (solver_host::record(ctx, st)) return -1;
     st->timed = true;
     return 0;
 }
 
-int32_t smrt_second_order_sync(smrt_dort_ctx* ctx) { return smrt_first_order_sync(ctx); }
+int32_t smrt_second_order_sync(smrt_dort_ctx* ctx) { return solver_host::sync(ctx); }
 
 int32_t smrt_second_order_kernel_ms(smrt_dort_ctx* ctx, double* ms2) {
     if (!ctx || !ms2) return -1;
     SecondOrderState* st = ctx->second_order;
     if (!st || !st->timed) { ctx->err = "no second-order launch to time"; return -1; }
-    HIPCHK(hipSetDevice(ctx->device));
-    HIPCHK(hipEventSynchronize(st->ev[2]));
-    float a = 0.f, c = 0.f;
-    HIPCHK(hipEventElapsedTime(&a, st->ev[0], st->ev[1]));
-    HIPCHK(hipEventElapsedTime(&c, st->ev[1], st->ev[2]));
-    ms2[0] = a; ms2[1] = c;
+    ms2[0] = ms2[1] = 0.0;
+    if (solver_host::wait_recorded(ctx, st) || solver_host::add_elapsed(ctx, st, 0, 1, &ms2[0]) || solver_host::add_elapsed(ctx, st, 1, 2, &ms2[1])) return -1;
     return 0;
 }
 

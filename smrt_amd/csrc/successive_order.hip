@@ -10,21 +10,11 @@
 #include <string>
 #include <vector>
 
-#include "dort_ctx.hpp"
-#include "dort_host_common.hpp"
 #include "successive_order_kernel.hpp"
-#include "../../include/smrt_dort.h"
+#include "solver_host.hpp"
+#include "solver_refusals.hpp"
 
 using namespace smrt;
-
-#define HIPCHK(call)                                                                              \
-    do {                                                                                          \
-        hipError_t e_ = (call);                                                                   \
-        if (e_ != hipSuccess) {                                                                   \
-            ctx->err = std::string(#call) + ": " + hipGetErrorString(e_);                         \
-            return -1;                                                                            \
-        }                                                                                         \
-    } while (0)
 
 __global__ void __launch_bounds__(kSoThreads) successive_order_layers_kernel(SoBatch b) {
     const long long idx = (long long)blockIdx.x * kSoThreads + threadIdx.x;
@@ -42,9 +32,10 @@ __global__ void __launch_bounds__(kSoThreads) successive_order_sweep_kernel(SoBa
     so_sweep_pair<kSoThreads>(b, b.chunk_begin + blockIdx.x, so_lds);
 }
 
-struct SuccessiveOrderState {
-    DevBuf nl, thick, fv, temp, p1, p2, freq, theta, lw, kind, sub1, sub2, subT, gl, pairmap;
-    DevBuf stage, nsub, nstream, vec, srcterm, wsoff, chunk, out, status, layer, streams, maxrad, orders;
+struct SuccessiveOrderState : solver_host::InputState {
+    DevBuf &theta = buf(), &subT = buf(), &gl = buf();
+    DevBuf &stage = buf(), &nsub = buf(), &nstream = buf(), &vec = buf(), &srcterm = buf(), &wsoff = buf(), &chunk = buf(), &out = buf(),
+           &status = buf(), &layer = buf(), &streams = buf(), &maxrad = buf(), &orders = buf();
     SoBatch dev{};
     bool uploaded = false, launched = false;
     int64_t budget = 0;
@@ -52,84 +43,14 @@ struct SuccessiveOrderState {
     size_t chunk_bytes = 0;             // the chunk buffer (Wt + workspace of the largest chunk)
     std::vector<int32_t> nsub_host;     // [n_pairs][Lmax] after a launch
     std::vector<long long> deep;        // rows that do not fit the budget
-    int64_t n_chunks = 0;
-    std::vector<hipEvent_t> ev;         // pool
-    size_t ev_used = 0;                 // [0, 1]: layers kernel; then three per chunk
+    int64_t n_chunks = 0;               // events 0, 1: layers kernel; then three per chunk
 };
 
 constexpr int64_t kSoDefaultBudget = 8LL << 30;
 
 namespace smrt_launch {
-void successive_order_release(smrt_dort_ctx* ctx) {
-    SuccessiveOrderState* st = ctx->successive_order;
-    if (!st) return;
-    DevBuf* bufs[] = {&st->nl, &st->thick, &st->fv, &st->temp, &st->p1, &st->p2, &st->freq, &st->theta, &st->lw, &st->kind, &st->sub1,
-                      &st->sub2, &st->subT, &st->gl, &st->pairmap, &st->stage, &st->nsub, &st->nstream, &st->vec, &st->srcterm,
-                      &st->wsoff, &st->chunk, &st->out, &st->status, &st->layer, &st->streams, &st->maxrad, &st->orders};
-    for (DevBuf* b : bufs) b->release();
-    for (hipEvent_t e : st->ev) if (e) (void)hipEventDestroy(e);
-    delete st;
-    ctx->successive_order = nullptr;
-}
+void successive_order_release(smrt_dort_ctx* ctx) { solver_host::release(ctx->successive_order); }
 }  // namespace smrt_launch
-
-static const char* so_validate(const smrt_batch* b, int32_t n_iter, double rtol) {
-    if (!b) return "null batch";
-    if (b->n_snowpacks <= 0 || b->n_frequencies <= 0 || b->n_layers_max <= 0) return "empty batch";
-    if (b->n_theta <= 0) return "n_theta must be positive";
-    if (b->mode != SMRT_MODE_PASSIVE) return "the successive_order solver needs a passive sensor";
-    if (n_iter < 1) return "n_iteration_max must be at least 1";
-    if (!(rtol >= 0.0)) return "relative_tolerance must be non-negative";
-    if (b->n_max_stream < 2 || b->n_max_stream > kSoMaxStream) return "the successive_order solver takes 2 to 64 streams";
-    if (b->m_max < 0) return "m_max must be non-negative";
-    if (b->emmodel < SMRT_EM_IBA || b->emmodel > SMRT_EM_RAYLEIGH_HOST) return "unknown emmodel";
-    if (b->microstructure < SMRT_MS_EXPONENTIAL || b->microstructure > SMRT_MS_TEUBNER_STREY) return "unknown microstructure";
-    if (!b->n_layers || !b->thickness || !b->frac_volume || !b->temperature || !b->micro_p1 || !b->frequency || !b->theta)
-        return "null input array";
-    if ((b->microstructure == SMRT_MS_STICKY_HARD_SPHERES || b->layer_kind) && !b->micro_p2) return "stickiness array missing";
-    const char* host = "the successive_order solver has no route for emmodels evaluated on the host";
-    if (!b->layer_kind) {
-        if (b->emmodel == SMRT_EM_HOST || b->emmodel == SMRT_EM_IBA_HOST || b->emmodel == SMRT_EM_RAYLEIGH_HOST) return host;
-        if ((b->emmodel == SMRT_EM_DMRT_QCA_SHORTRANGE || b->emmodel == SMRT_EM_DMRT_QCACP_SHORTRANGE) &&
-            b->microstructure != SMRT_MS_STICKY_HARD_SPHERES)
-            return "the dmrt short-range emmodels are only compatible with sticky_hard_spheres";
-    }
-    for (int s = 0; s < b->n_snowpacks; ++s) {
-        if (b->n_layers[s] < 1 || b->n_layers[s] > b->n_layers_max) return "n_layers out of range";
-        for (int l = 0; b->layer_kind && l < b->n_layers[s]; ++l) {
-            const int k = b->layer_kind[(long long)s * b->n_layers_max + l], em = k & 15, ms = k >> 4;
-            if (em < SMRT_EM_IBA || em > SMRT_EM_RAYLEIGH_HOST || ms < SMRT_MS_EXPONENTIAL || ms > SMRT_MS_TEUBNER_STREY)
-                return "invalid layer_kind entry";
-            if (em == SMRT_EM_HOST || em == SMRT_EM_IBA_HOST || em == SMRT_EM_RAYLEIGH_HOST) return host;
-            if ((em == SMRT_EM_DMRT_QCA_SHORTRANGE || em == SMRT_EM_DMRT_QCACP_SHORTRANGE) && ms != SMRT_MS_STICKY_HARD_SPHERES)
-                return "the dmrt short-range emmodels are only compatible with sticky_hard_spheres";
-        }
-    }
-    if (b->substrate_kind < SMRT_SUBSTRATE_NONE || b->substrate_kind > SMRT_SUBSTRATE_REFLECTOR)
-        return "the successive_order solver takes no substrate, a flat one or a reflector";
-    if (b->substrate_kind != SMRT_SUBSTRATE_NONE && (!b->substrate_p1 || !b->substrate_p2)) return "substrate arrays missing";
-    if (b->host_interface_slot) return "the successive_order solver takes flat interfaces only";
-    if (b->atm_tb_down || b->atm_tb_up || b->atm_transmittance) return "the successive_order solver can not handle atmosphere yet.";
-    if (b->process_coherent_layers) return "the successive_order solver does not process coherent layers";
-    return nullptr;
-}
-
-static int so_upload(smrt_dort_ctx* ctx, DevBuf& buf, const void* src, size_t bytes, size_t* total) {
-    HIPCHK(buf.reserve(bytes));
-    HIPCHK(hipMemcpyAsync(buf.p, src, bytes, hipMemcpyHostToDevice, ctx->stream));
-    *total += bytes;
-    return 0;
-}
-
-static int so_event(smrt_dort_ctx* ctx, SuccessiveOrderState* st) {
-    if (st->ev_used == st->ev.size()) {
-        hipEvent_t e = nullptr;
-        HIPCHK(hipEventCreate(&e));
-        st->ev.push_back(e);
-    }
-    HIPCHK(hipEventRecord(st->ev[st->ev_used++], ctx->stream));
-    return 0;
-}
 
 extern "C" {
 
@@ -141,15 +62,9 @@ int32_t smrt_successive_order_upload_pairs(smrt_dort_ctx* ctx, const smrt_batch*
                                            double relative_tolerance, int64_t workspace_budget_bytes, const int64_t* pairs,
                                            int64_t n_pairs) {
     if (!ctx) return -1;
-    const char* why = so_validate(b, n_iteration_max, relative_tolerance);
+    const char* why = solver_refusals::successive_order(b, n_iteration_max, relative_tolerance);
     if (why) { ctx->err = why; return -1; }
-    const int64_t all = (int64_t)b->n_snowpacks * b->n_frequencies;
-    if (!pairs) n_pairs = all;
-    else {
-        if (n_pairs <= 0) { ctx->err = "empty pair list"; return -1; }
-        for (int64_t i = 0; i < n_pairs; ++i)
-            if (pairs[i] < 0 || pairs[i] >= all) { ctx->err = "pair index out of bounds"; return -1; }
-    }
+    if (solver_host::check_pairs(ctx, pairs, &n_pairs, (int64_t)b->n_snowpacks * b->n_frequencies)) return -1;
     HIPCHK(hipSetDevice(ctx->device));
     if (!ctx->successive_order) ctx->successive_order = new SuccessiveOrderState();
     SuccessiveOrderState* st = ctx->successive_order;
@@ -175,30 +90,15 @@ int32_t smrt_successive_order_upload_pairs(smrt_dort_ctx* ctx, const smrt_batch*
     d.n_iter = n_iteration_max; d.rj = b->rayleigh_jeans ? 1 : 0; d.nsamp = azimuth_samples(b->m_max);
     d.rtol = relative_tolerance;
     d.n_pairs = n_pairs;
-    size_t up = 0;
-#define SO_UP(buf, src, bytes, field) do { if (so_upload(ctx, st->buf, src, bytes, &up)) return -1; d.field = (decltype(d.field))st->buf.p; } while (0)
-    SO_UP(nl, b->n_layers, S * sizeof(int32_t), n_layers);
-    SO_UP(thick, b->thickness, SL, thickness);
-    SO_UP(fv, b->frac_volume, SL, frac_volume);
-    SO_UP(temp, b->temperature, SL, temperature);
-    SO_UP(p1, b->micro_p1, SL, p1);
-    if (b->micro_p2) SO_UP(p2, b->micro_p2, SL, p2);
-    SO_UP(freq, b->frequency, F * sizeof(double), frequency);
-    SO_UP(theta, b->theta, T * sizeof(double), theta);
-    if (b->liquid_water) SO_UP(lw, b->liquid_water, SL, liquid_water);
-    if (b->layer_kind) SO_UP(kind, b->layer_kind, S * L * sizeof(int32_t), layer_kind);
-    std::vector<double> subT(S, 0.0);
-    if (b->substrate_kind != SMRT_SUBSTRATE_NONE) {
-        SO_UP(sub1, b->substrate_p1, FS * sizeof(double), sub_p1);
-        SO_UP(sub2, b->substrate_p2, FS * sizeof(double), sub_p2);
-        for (size_t s = 0; s < S && b->substrate_temperature; ++s) subT[s] = b->substrate_temperature[s];
-        SO_UP(subT, subT.data(), S * sizeof(double), sub_T);
-    }
+    using solver_host::upload;
+    if (solver_host::upload_batch(ctx, st, b, pairs, d)) return -1;
+    if (upload(ctx, st->theta, b->theta, T * sizeof(double), d.theta)) return -1;
+    std::vector<double> subT(S, 0.0);   // (zeros where the caller gives no substrate temperature)
+    for (size_t s = 0; s < S && b->substrate_temperature; ++s) subT[s] = b->substrate_temperature[s];
+    if (b->substrate_kind != SMRT_SUBSTRATE_NONE && upload(ctx, st->subT, subT.data(), S * sizeof(double), d.sub_T)) return -1;
     std::vector<double> gl(NM);
     smrt_host::gauss_legendre_positive((int)NM, gl.data(), nullptr);
-    SO_UP(gl, gl.data(), NM * sizeof(double), gl_mu);
-    if (pairs) SO_UP(pairmap, pairs, N * sizeof(int64_t), pair_map);
-#undef SO_UP
+    if (upload(ctx, st->gl, gl.data(), NM * sizeof(double), d.gl_mu)) return -1;
     DevBuf* outs[] = {&st->stage, &st->nsub, &st->nstream, &st->vec, &st->srcterm, &st->wsoff, &st->out, &st->status, &st->layer,
                       &st->streams, &st->maxrad, &st->orders};
     for (size_t k = 0; k < sizeof(outs) / sizeof(outs[0]); ++k) HIPCHK(outs[k]->reserve(out_bytes[k]));
@@ -206,8 +106,7 @@ int32_t smrt_successive_order_upload_pairs(smrt_dort_ctx* ctx, const smrt_batch*
     d.srcterm = (double*)st->srcterm.p; d.ws_off = (const long long*)st->wsoff.p; d.out = (double*)st->out.p;
     d.status = (int*)st->status.p; d.layer_out = (double*)st->layer.p; d.streams = (double*)st->streams.p;
     d.maxrad = (double*)st->maxrad.p; d.orders = (int*)st->orders.p;
-    // the copies above read the caller's (pageable) arrays and this function's own vectors: wait for them
-    HIPCHK(hipStreamSynchronize(ctx->stream));
+    if (solver_host::uploads_done(ctx)) return -1;
     st->fixed_bytes = fixed;
     st->dev = d;
     st->uploaded = true;
@@ -222,14 +121,14 @@ int32_t smrt_successive_order_launch(smrt_dort_ctx* ctx) {
     SoBatch d = st->dev;
     const long long N = d.n_pairs, L = d.Lmax;
     st->launched = false;
-    st->ev_used = 0;
+    st->rewind();
     st->deep.clear();
     // (a) layer scalars and sublayer counts; the counts come back: they size the workspace
-    if (so_event(ctx, st)) return -1;
+    if (solver_host::record(ctx, st)) return -1;
     hipLaunchKernelGGL(successive_order_layers_kernel, dim3((unsigned)((N * L + kSoThreads - 1) / kSoThreads)), dim3(kSoThreads), 0,
                        ctx->stream, d);
     HIPCHK(hipGetLastError());
-    if (so_event(ctx, st)) return -1;
+    if (solver_host::record(ctx, st)) return -1;
     st->nsub_host.resize((size_t)(N * L));
     HIPCHK(hipMemcpyAsync(st->nsub_host.data(), d.nsub, (size_t)(N * L) * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
     HIPCHK(hipStreamSynchronize(ctx->stream));
@@ -266,40 +165,28 @@ int32_t smrt_successive_order_launch(smrt_dort_ctx* ctx) {
         d.chunk_begin = begin[c]; d.chunk_count = count[c];
         d.wt = (double*)st->chunk.p;
         d.ws = d.wt + count[c] * wt_pair;
-        if (so_event(ctx, st)) return -1;
+        if (solver_host::record(ctx, st)) return -1;
         hipLaunchKernelGGL(successive_order_prep_kernel, dim3((unsigned)(count[c] * L)), dim3(kSoThreads), 0, ctx->stream, d);
         HIPCHK(hipGetLastError());
-        if (so_event(ctx, st)) return -1;
+        if (solver_host::record(ctx, st)) return -1;
         hipLaunchKernelGGL(successive_order_sweep_kernel, dim3((unsigned)count[c]), dim3(kSoThreads), lds, ctx->stream, d);
         HIPCHK(hipGetLastError());
-        if (so_event(ctx, st)) return -1;
+        if (solver_host::record(ctx, st)) return -1;
     }
     st->launched = true;
     return 0;
 }
 
-int32_t smrt_successive_order_sync(smrt_dort_ctx* ctx) {
-    if (!ctx) return -1;
-    HIPCHK(hipSetDevice(ctx->device));
-    HIPCHK(hipStreamSynchronize(ctx->stream));
-    return 0;
-}
+int32_t smrt_successive_order_sync(smrt_dort_ctx* ctx) { return solver_host::sync(ctx); }
 
 int32_t smrt_successive_order_kernel_ms(smrt_dort_ctx* ctx, double* ms2) {
     if (!ctx || !ms2) return -1;
     SuccessiveOrderState* st = ctx->successive_order;
     if (!st || !st->launched) { ctx->err = "no successive-order launch to time"; return -1; }
-    HIPCHK(hipSetDevice(ctx->device));
-    HIPCHK(hipEventSynchronize(st->ev[st->ev_used - 1]));
-    float a = 0.f;
-    HIPCHK(hipEventElapsedTime(&a, st->ev[0], st->ev[1]));
-    double prep = a, sweep = 0.0;
-    for (size_t k = 2; k + 2 < st->ev_used; k += 3) {
-        HIPCHK(hipEventElapsedTime(&a, st->ev[k], st->ev[k + 1]));
-        prep += a;
-        HIPCHK(hipEventElapsedTime(&a, st->ev[k + 1], st->ev[k + 2]));
-        sweep += a;
-    }
+    double prep = 0.0, sweep = 0.0;
+    if (solver_host::wait_recorded(ctx, st) || solver_host::add_elapsed(ctx, st, 0, 1, &prep)) return -1;
+    for (size_t k = 2; k + 2 < st->ev_used; k += 3)
+        if (solver_host::add_elapsed(ctx, st, k, k + 1, &prep) || solver_host::add_elapsed(ctx, st, k + 1, k + 2, &sweep)) return -1;
     ms2[0] = prep; ms2[1] = sweep;
     return 0;
 }
@@ -309,9 +196,7 @@ int32_t smrt_successive_order_launch_info(smrt_dort_ctx* ctx, int64_t* info, int
     SuccessiveOrderState* st = ctx->successive_order;
     if (!st || !st->launched) { ctx->err = "no successive-order launch to describe"; return -1; }
     const int64_t v[] = {st->n_chunks, (int64_t)(st->fixed_bytes + st->chunk_bytes), (int64_t)st->deep.size(), st->budget};
-    const int32_t n = (int32_t)(sizeof(v) / sizeof(v[0]));
-    for (int32_t i = 0; info && i < n && i < capacity; ++i) info[i] = v[i];
-    return n;
+    return solver_host::copy_table(v, info, capacity);
 }
 
 int32_t smrt_successive_order_download(smrt_dort_ctx* ctx, double* out, int32_t* status, double* layer_out, double* streams,

@@ -11,21 +11,11 @@
 #include <string>
 #include <vector>
 
-#include "dort_ctx.hpp"
-#include "dort_host_common.hpp"
 #include "successive_order_active_kernel.hpp"
-#include "../../include/smrt_dort.h"
+#include "solver_host.hpp"
+#include "solver_refusals.hpp"
 
 using namespace smrt;
-
-#define HIPCHK(call)                                                                              \
-    do {                                                                                          \
-        hipError_t e_ = (call);                                                                   \
-        if (e_ != hipSuccess) {                                                                   \
-            ctx->err = std::string(#call) + ": " + hipGetErrorString(e_);                         \
-            return -1;                                                                            \
-        }                                                                                         \
-    } while (0)
 
 __global__ void __launch_bounds__(kSoaThreads) successive_order_active_layers_kernel(SoaBatch a) {
     const long long idx = (long long)blockIdx.x * kSoaThreads + threadIdx.x;
@@ -52,9 +42,10 @@ __global__ void __launch_bounds__(kSoaThreads) successive_order_active_combine_k
     soa_combine_item(a, a.so.chunk_begin + idx / row, (int)(idx % row));
 }
 
-struct SuccessiveOrderActiveState {
-    DevBuf nl, thick, fv, temp, p1, p2, freq, theta, lw, kind, sub1, sub2, gl, pairmap;
-    DevBuf stage, nsub, nstream, vec, air, wsoff, chunk, out, status, layer, streams, maxrad, orders, back, inc;
+struct SuccessiveOrderActiveState : solver_host::InputState {
+    DevBuf &theta = buf(), &gl = buf();
+    DevBuf &stage = buf(), &nsub = buf(), &nstream = buf(), &vec = buf(), &air = buf(), &wsoff = buf(), &chunk = buf(), &out = buf(),
+           &status = buf(), &layer = buf(), &streams = buf(), &maxrad = buf(), &orders = buf(), &back = buf(), &inc = buf();
     SoaBatch dev{};
     bool uploaded = false, launched = false;
     int64_t budget = 0;
@@ -62,87 +53,14 @@ struct SuccessiveOrderActiveState {
     size_t chunk_bytes = 0;             // the chunk buffer (Wt + workspace of the largest chunk)
     std::vector<int32_t> nsub_host;     // [n_pairs][Lmax] after a launch
     std::vector<long long> deep;        // rows that do not fit the budget
-    int64_t n_chunks = 0;
-    std::vector<hipEvent_t> ev;         // pool
-    size_t ev_used = 0;                 // [0, 1]: layers kernel; then four per chunk
+    int64_t n_chunks = 0;               // events 0, 1: layers kernel; then four per chunk
 };
 
 constexpr int64_t kSoaDefaultBudget = 8LL << 30;
 
 namespace smrt_launch {
-void successive_order_active_release(smrt_dort_ctx* ctx) {
-    SuccessiveOrderActiveState* st = ctx->successive_order_active;
-    if (!st) return;
-    DevBuf* bufs[] = {&st->nl, &st->thick, &st->fv, &st->temp, &st->p1, &st->p2, &st->freq, &st->theta, &st->lw, &st->kind, &st->sub1,
-                      &st->sub2, &st->gl, &st->pairmap, &st->stage, &st->nsub, &st->nstream, &st->vec, &st->air, &st->wsoff,
-                      &st->chunk, &st->out, &st->status, &st->layer, &st->streams, &st->maxrad, &st->orders, &st->back, &st->inc};
-    for (DevBuf* b : bufs) b->release();
-    for (hipEvent_t e : st->ev) if (e) (void)hipEventDestroy(e);
-    delete st;
-    ctx->successive_order_active = nullptr;
-}
+void successive_order_active_release(smrt_dort_ctx* ctx) { solver_host::release(ctx->successive_order_active); }
 }  // namespace smrt_launch
-
-static const char* soa_validate(const smrt_batch* b, int32_t n_iter, double rtol, int32_t n_theta_inc, const double* theta_inc,
-                                int32_t incident_npol, int32_t m_max) {
-    if (!b) return "null batch";
-    if (b->n_snowpacks <= 0 || b->n_frequencies <= 0 || b->n_layers_max <= 0) return "empty batch";
-    if (n_theta_inc <= 0 || !theta_inc) return "n_theta_inc must be positive";
-    if (b->mode != SMRT_MODE_ACTIVE) return "the successive_order_backscatter solver needs an active sensor";
-    if (n_iter < 1) return "n_iteration_max must be at least 1";
-    if (!(rtol >= 0.0)) return "relative_tolerance must be non-negative";
-    if (incident_npol < 1 || incident_npol > 3) return "incident_npol must be 1 (V), 2 (VH) or 3 (VHU)";
-    if (b->n_max_stream < 2 || b->n_max_stream > kSoMaxStream) return "the successive_order_backscatter solver takes 2 to 64 streams";
-    if (m_max < 0 || m_max > 64) return "m_max must be 0 to 64";
-    if (b->emmodel < SMRT_EM_IBA || b->emmodel > SMRT_EM_RAYLEIGH_HOST) return "unknown emmodel";
-    if (b->microstructure < SMRT_MS_EXPONENTIAL || b->microstructure > SMRT_MS_TEUBNER_STREY) return "unknown microstructure";
-    if (!b->n_layers || !b->thickness || !b->frac_volume || !b->temperature || !b->micro_p1 || !b->frequency) return "null input array";
-    if ((b->microstructure == SMRT_MS_STICKY_HARD_SPHERES || b->layer_kind) && !b->micro_p2) return "stickiness array missing";
-    const char* host = "the successive_order_backscatter solver has no route for emmodels evaluated on the host";
-    const char* shs = "the dmrt short-range emmodels are only compatible with sticky_hard_spheres";
-    const char* rayleigh = "the Rayleigh-family emmodels have azimuth modes 0 to 2 only: m_max must be at most 2";
-    if (!b->layer_kind) {
-        if (b->emmodel == SMRT_EM_HOST || b->emmodel == SMRT_EM_IBA_HOST || b->emmodel == SMRT_EM_RAYLEIGH_HOST) return host;
-        const bool dmrt = b->emmodel == SMRT_EM_DMRT_QCA_SHORTRANGE || b->emmodel == SMRT_EM_DMRT_QCACP_SHORTRANGE;
-        if (dmrt && b->microstructure != SMRT_MS_STICKY_HARD_SPHERES) return shs;
-        if (dmrt && m_max > 2) return rayleigh;
-    }
-    for (int s = 0; s < b->n_snowpacks; ++s) {
-        if (b->n_layers[s] < 1 || b->n_layers[s] > b->n_layers_max) return "n_layers out of range";
-        for (int l = 0; b->layer_kind && l < b->n_layers[s]; ++l) {
-            const int k = b->layer_kind[(long long)s * b->n_layers_max + l], em = k & 15, ms = k >> 4;
-            if (em < SMRT_EM_IBA || em > SMRT_EM_RAYLEIGH_HOST || ms < SMRT_MS_EXPONENTIAL || ms > SMRT_MS_TEUBNER_STREY)
-                return "invalid layer_kind entry";
-            if (em == SMRT_EM_HOST || em == SMRT_EM_IBA_HOST || em == SMRT_EM_RAYLEIGH_HOST) return host;
-            const bool dmrt = em == SMRT_EM_DMRT_QCA_SHORTRANGE || em == SMRT_EM_DMRT_QCACP_SHORTRANGE;
-            if (dmrt && ms != SMRT_MS_STICKY_HARD_SPHERES) return shs;
-            if (dmrt && m_max > 2) return rayleigh;
-        }
-    }
-    if (b->substrate_kind != SMRT_SUBSTRATE_NONE && b->substrate_kind != SMRT_SUBSTRATE_FLAT)
-        return "the successive_order_backscatter solver takes no substrate or a flat one (a reflector has no third Stokes component)";
-    if (b->substrate_kind != SMRT_SUBSTRATE_NONE && (!b->substrate_p1 || !b->substrate_p2)) return "substrate arrays missing";
-    if (b->host_interface_slot) return "the successive_order_backscatter solver takes flat interfaces only";
-    if (b->process_coherent_layers) return "the successive_order_backscatter solver does not process coherent layers";
-    return nullptr;
-}
-
-static int soa_upload(smrt_dort_ctx* ctx, DevBuf& buf, const void* src, size_t bytes, size_t* total) {
-    HIPCHK(buf.reserve(bytes));
-    HIPCHK(hipMemcpyAsync(buf.p, src, bytes, hipMemcpyHostToDevice, ctx->stream));
-    *total += bytes;
-    return 0;
-}
-
-static int soa_event(smrt_dort_ctx* ctx, SuccessiveOrderActiveState* st) {
-    if (st->ev_used == st->ev.size()) {
-        hipEvent_t e = nullptr;
-        HIPCHK(hipEventCreate(&e));
-        st->ev.push_back(e);
-    }
-    HIPCHK(hipEventRecord(st->ev[st->ev_used++], ctx->stream));
-    return 0;
-}
 
 extern "C" {
 
@@ -155,15 +73,9 @@ int32_t smrt_so_active_upload_pairs(smrt_dort_ctx* ctx, const smrt_batch* b, int
                                                   int32_t incident_npol, int32_t m_max, int64_t workspace_budget_bytes,
                                                   const int64_t* pairs, int64_t n_pairs) {
     if (!ctx) return -1;
-    const char* why = soa_validate(b, n_iteration_max, relative_tolerance, n_theta_inc, theta_inc, incident_npol, m_max);
+    const char* why = solver_refusals::successive_order_active(b, n_iteration_max, relative_tolerance, n_theta_inc, theta_inc, incident_npol, m_max);
     if (why) { ctx->err = why; return -1; }
-    const int64_t all = (int64_t)b->n_snowpacks * b->n_frequencies;
-    if (!pairs) n_pairs = all;
-    else {
-        if (n_pairs <= 0) { ctx->err = "empty pair list"; return -1; }
-        for (int64_t i = 0; i < n_pairs; ++i)
-            if (pairs[i] < 0 || pairs[i] >= all) { ctx->err = "pair index out of bounds"; return -1; }
-    }
+    if (solver_host::check_pairs(ctx, pairs, &n_pairs, (int64_t)b->n_snowpacks * b->n_frequencies)) return -1;
     HIPCHK(hipSetDevice(ctx->device));
     if (!ctx->successive_order_active) ctx->successive_order_active = new SuccessiveOrderActiveState();
     SuccessiveOrderActiveState* st = ctx->successive_order_active;
@@ -192,27 +104,12 @@ int32_t smrt_so_active_upload_pairs(smrt_dort_ctx* ctx, const smrt_batch* b, int
     d.rtol = relative_tolerance;
     d.n_pairs = n_pairs;
     a.npi = incident_npol; a.m_max = m_max; a.Cmax = (int)CM; a.phi = b->phi;
-    size_t up = 0;
-#define SO_UP(buf, src, bytes, field) do { if (soa_upload(ctx, st->buf, src, bytes, &up)) return -1; d.field = (decltype(d.field))st->buf.p; } while (0)
-    SO_UP(nl, b->n_layers, S * sizeof(int32_t), n_layers);
-    SO_UP(thick, b->thickness, SL, thickness);
-    SO_UP(fv, b->frac_volume, SL, frac_volume);
-    SO_UP(temp, b->temperature, SL, temperature);
-    SO_UP(p1, b->micro_p1, SL, p1);
-    if (b->micro_p2) SO_UP(p2, b->micro_p2, SL, p2);
-    SO_UP(freq, b->frequency, F * sizeof(double), frequency);
-    SO_UP(theta, theta_inc, T * sizeof(double), theta);
-    if (b->liquid_water) SO_UP(lw, b->liquid_water, SL, liquid_water);
-    if (b->layer_kind) SO_UP(kind, b->layer_kind, S * L * sizeof(int32_t), layer_kind);
-    if (b->substrate_kind != SMRT_SUBSTRATE_NONE) {
-        SO_UP(sub1, b->substrate_p1, FS * sizeof(double), sub_p1);
-        SO_UP(sub2, b->substrate_p2, FS * sizeof(double), sub_p2);
-    }
+    using solver_host::upload;
+    if (solver_host::upload_batch(ctx, st, b, pairs, d)) return -1;
+    if (upload(ctx, st->theta, theta_inc, T * sizeof(double), d.theta)) return -1;
     std::vector<double> gl(NM);
     smrt_host::gauss_legendre_positive((int)NM, gl.data(), nullptr);
-    SO_UP(gl, gl.data(), NM * sizeof(double), gl_mu);
-    if (pairs) SO_UP(pairmap, pairs, N * sizeof(int64_t), pair_map);
-#undef SO_UP
+    if (upload(ctx, st->gl, gl.data(), NM * sizeof(double), d.gl_mu)) return -1;
     DevBuf* outs[] = {&st->stage, &st->nsub, &st->nstream, &st->vec, &st->air, &st->wsoff, &st->out, &st->status, &st->layer,
                       &st->streams, &st->maxrad, &st->orders, &st->back, &st->inc};
     for (size_t k = 0; k < sizeof(outs) / sizeof(outs[0]); ++k) HIPCHK(outs[k]->reserve(out_bytes[k]));
@@ -220,8 +117,7 @@ int32_t smrt_so_active_upload_pairs(smrt_dort_ctx* ctx, const smrt_batch* b, int
     a.air = (double*)st->air.p; d.ws_off = (const long long*)st->wsoff.p; d.out = (double*)st->out.p;
     d.status = (int*)st->status.p; d.layer_out = (double*)st->layer.p; d.streams = (double*)st->streams.p;
     d.maxrad = (double*)st->maxrad.p; d.orders = (int*)st->orders.p; a.back = (double*)st->back.p; a.inc = (int*)st->inc.p;
-    // the copies above read the caller's (pageable) arrays and this function's own vectors: wait for them
-    HIPCHK(hipStreamSynchronize(ctx->stream));
+    if (solver_host::uploads_done(ctx)) return -1;
     st->fixed_bytes = fixed;
     st->dev = a;
     st->uploaded = true;
@@ -237,14 +133,14 @@ int32_t smrt_so_active_launch(smrt_dort_ctx* ctx) {
     SoBatch& d = a.so;
     const long long N = d.n_pairs, L = d.Lmax, M = a.m_max + 1, NP = a.m_max + 2;
     st->launched = false;
-    st->ev_used = 0;
+    st->rewind();
     st->deep.clear();
     // (a) layer scalars and sublayer counts; the counts come back: they size the workspace
-    if (soa_event(ctx, st)) return -1;
+    if (solver_host::record(ctx, st)) return -1;
     hipLaunchKernelGGL(successive_order_active_layers_kernel, dim3((unsigned)((N * L + kSoaThreads - 1) / kSoaThreads)), dim3(kSoaThreads), 0,
                        ctx->stream, a);
     HIPCHK(hipGetLastError());
-    if (soa_event(ctx, st)) return -1;
+    if (solver_host::record(ctx, st)) return -1;
     st->nsub_host.resize((size_t)(N * L));
     HIPCHK(hipMemcpyAsync(st->nsub_host.data(), d.nsub, (size_t)(N * L) * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
     HIPCHK(hipStreamSynchronize(ctx->stream));
@@ -283,46 +179,34 @@ int32_t smrt_so_active_launch(smrt_dort_ctx* ctx) {
         d.chunk_begin = begin[c]; d.chunk_count = count[c];
         d.wt = (double*)st->chunk.p;
         d.ws = d.wt + count[c] * wt_pair;
-        if (soa_event(ctx, st)) return -1;
+        if (solver_host::record(ctx, st)) return -1;
         hipLaunchKernelGGL(successive_order_active_prep_kernel, dim3((unsigned)(count[c] * L * M)), dim3(kSoaThreads), 0, ctx->stream, a);
         HIPCHK(hipGetLastError());
-        if (soa_event(ctx, st)) return -1;
+        if (solver_host::record(ctx, st)) return -1;
         hipLaunchKernelGGL(successive_order_active_sweep_kernel, dim3((unsigned)(count[c] * NP)), dim3(kSoaThreads), lds, ctx->stream, a);
         HIPCHK(hipGetLastError());
-        if (soa_event(ctx, st)) return -1;
+        if (solver_host::record(ctx, st)) return -1;
         hipLaunchKernelGGL(successive_order_active_combine_kernel, dim3((unsigned)((count[c] * row + kSoaThreads - 1) / kSoaThreads)),
                            dim3(kSoaThreads), 0, ctx->stream, a);
         HIPCHK(hipGetLastError());
-        if (soa_event(ctx, st)) return -1;
+        if (solver_host::record(ctx, st)) return -1;
     }
     st->launched = true;
     return 0;
 }
 
-int32_t smrt_so_active_sync(smrt_dort_ctx* ctx) {
-    if (!ctx) return -1;
-    HIPCHK(hipSetDevice(ctx->device));
-    HIPCHK(hipStreamSynchronize(ctx->stream));
-    return 0;
-}
+int32_t smrt_so_active_sync(smrt_dort_ctx* ctx) { return solver_host::sync(ctx); }
 
 int32_t smrt_so_active_kernel_ms(smrt_dort_ctx* ctx, double* ms3) {
     if (!ctx || !ms3) return -1;
     SuccessiveOrderActiveState* st = ctx->successive_order_active;
     if (!st || !st->launched) { ctx->err = "no successive-order backscatter launch to time"; return -1; }
-    HIPCHK(hipSetDevice(ctx->device));
-    HIPCHK(hipEventSynchronize(st->ev[st->ev_used - 1]));
-    float f = 0.f;
-    HIPCHK(hipEventElapsedTime(&f, st->ev[0], st->ev[1]));
-    double prep = f, sweep = 0.0, combine = 0.0;
-    for (size_t k = 2; k + 3 < st->ev_used; k += 4) {
-        HIPCHK(hipEventElapsedTime(&f, st->ev[k], st->ev[k + 1]));
-        prep += f;
-        HIPCHK(hipEventElapsedTime(&f, st->ev[k + 1], st->ev[k + 2]));
-        sweep += f;
-        HIPCHK(hipEventElapsedTime(&f, st->ev[k + 2], st->ev[k + 3]));
-        combine += f;
-    }
+    double prep = 0.0, sweep = 0.0, combine = 0.0;
+    if (solver_host::wait_recorded(ctx, st) || solver_host::add_elapsed(ctx, st, 0, 1, &prep)) return -1;
+    for (size_t k = 2; k + 3 < st->ev_used; k += 4)
+        if (solver_host::add_elapsed(ctx, st, k, k + 1, &prep) || solver_host::add_elapsed(ctx, st, k + 1, k + 2, &sweep) ||
+            solver_host::add_elapsed(ctx, st, k + 2, k + 3, &combine))
+            return -1;
     ms3[0] = prep; ms3[1] = sweep; ms3[2] = combine;
     return 0;
 }
@@ -332,9 +216,7 @@ int32_t smrt_so_active_launch_info(smrt_dort_ctx* ctx, int64_t* info, int32_t ca
     SuccessiveOrderActiveState* st = ctx->successive_order_active;
     if (!st || !st->launched) { ctx->err = "no successive-order backscatter launch to describe"; return -1; }
     const int64_t v[] = {st->n_chunks, (int64_t)(st->fixed_bytes + st->chunk_bytes), (int64_t)st->deep.size(), st->budget};
-    const int32_t n = (int32_t)(sizeof(v) / sizeof(v[0]));
-    for (int32_t i = 0; info && i < n && i < capacity; ++i) info[i] = v[i];
-    return n;
+    return solver_host::copy_table(v, info, capacity);
 }
 
 int32_t smrt_so_active_download(smrt_dort_ctx* ctx, double* out, int32_t* status, double* layer_out, double* streams,
