@@ -770,6 +770,80 @@ int32_t smrt_lrm_kernel_ms(smrt_dort_ctx* ctx, double* ms3);
 /* [sizeof(smrt_lrm_params), offset of every field in declaration order] as compiled; returns the number of entries. */
 int32_t smrt_lrm_abi(int32_t* out, int32_t capacity);
 
+/*
+ * The nadir SAR altimetry solver (the reference's smrt/rtsolver/nadir_sar_altimetry.py with the Dinardo et al. 2018 delay-Doppler
+ * model of delay_doppler_model/dinardo18.py) on the same context: the delay-Doppler map of a SAR altimeter over a layered
+ * snowpack.  It reads of the smrt_batch what the LRM solver reads, and takes ONE frequency per batch.  What one group of pairs
+ * shares is in smrt_sar_params:
+ *   altitude, pulse_bandwidth, nominal_gate, pulse_repetition_frequency, wavelength, velocity, alpha   the sensor's;
+ *   pitch_angle, roll_angle   radians;
+ *   sigma_p, theta_lim, gamma_x, gamma_y, l_gamma, lz, pu   the constants of the model (D18 eq. 18, 19, 27; R15 eq. 37);
+ *   nu_coherent      one over the square decay of the coherent reflection (Fung and Eom 1983);
+ *   ngate, ndoppler, oversampling_time, oversampling_doppler   the oversampled map has ngate x oversampling_time delays and
+ *                    ndoppler x oversampling_doppler Doppler frequencies (ndoppler even);
+ *   return_oversampled   the oversampled map instead of the mean over every oversampling block;
+ *   n_rows           output rows per pair;
+ *   n_tables, table_sigma [n_tables], table_index [n_snowpacks]   the distinct sigma_surface (metres) and the one of every snowpack;
+ *   boundary_values  [n_snowpacks][n_layers_max + 1][4] per boundary (slot n_layers of a snowpack is the substrate): the one-way
+ *                    power transmission at nadir (NaN: Flat, on the device; -1: transparent), the coherent and the incoherent
+ *                    echo before attenuation, one over the mean square slope (0 where the incoherent echo is 0);
+ *   row_map          [n_snowpacks][2 (n_layers_max + 1) + 2] the output row (or -1) of the incoherent echo of every boundary, of the
+ *                    coherent echo of every boundary and of the volume; then the row of the total, which takes every source.
+ * Outputs, one row per pair: out [n_rows][delays][Doppler frequencies] (smrt_sar_out_stride doubles); status [1] SMRT_OK or
+ * SMRT_ERR_INPUT (invalid layers, or a boundary with a positive echo later than the window: the map is NaN then); optional
+ * (may be NULL) z_gate [delays] (NaN below the snowpack), layer_out [n_layers_max][5] as the LRM solver's, vertical
+ * [ngate x oversampling_time] the volume backscatter per sub-gate, echo [n_layers_max + 1][4] per boundary: two-way travel
+ * time, attenuated coherent and incoherent echo, shift in samples.  The maps of one launch stay below 2 GiB: more pairs are refused.
+ */
+typedef struct smrt_sar_params {
+    double altitude;
+    double pulse_bandwidth;
+    double nominal_gate;
+    double pulse_repetition_frequency;
+    double wavelength;
+    double velocity;
+    double alpha;
+    double pitch_angle;
+    double roll_angle;
+    double sigma_p;
+    double theta_lim;
+    double gamma_x;
+    double gamma_y;
+    double l_gamma;
+    double lz;
+    double pu;
+    double nu_coherent;
+    int32_t ngate;
+    int32_t ndoppler;
+    int32_t oversampling_time;
+    int32_t oversampling_doppler;
+    int32_t return_oversampled;
+    int32_t n_rows;
+    int32_t n_tables;
+    int32_t reserved;
+    const double* table_sigma;
+    const int32_t* table_index;
+    const double* boundary_values;
+    const int32_t* row_map;
+} smrt_sar_params;
+/* Doubles per pair of `out` (negative: invalid parameters). */
+int32_t smrt_sar_out_stride(const smrt_sar_params* p);
+/* One shot over the listed pairs (semantics of smrt_dort_run_pairs; pairs == NULL: every pair of the batch in order,
+ * n_pairs ignored).  Returns 0, negative on error. */
+int32_t smrt_sar_run_pairs(smrt_dort_ctx* ctx, const smrt_batch* batch, const smrt_sar_params* params, const int64_t* pairs,
+                           int64_t n_pairs, double* out, int32_t* status, double* z_gate, double* layer_out, double* vertical, double* echo);
+/* Split form: upload once, launch (asynchronous on the context's stream) any number of times, sync, download. */
+int32_t smrt_sar_upload_pairs(smrt_dort_ctx* ctx, const smrt_batch* batch, const smrt_sar_params* params, const int64_t* pairs,
+                              int64_t n_pairs);
+int32_t smrt_sar_launch(smrt_dort_ctx* ctx);
+int32_t smrt_sar_sync(smrt_dort_ctx* ctx);
+int32_t smrt_sar_download(smrt_dort_ctx* ctx, double* out, int32_t* status, double* z_gate, double* layer_out, double* vertical, double* echo);
+/* HIP-event time (ms) of the four kernels of the last launch, after a sync: layer scalars, vertical distribution and echoes,
+ * f0 / f1 tables, map. */
+int32_t smrt_sar_kernel_ms(smrt_dort_ctx* ctx, double* ms4);
+/* [sizeof(smrt_sar_params), offset of every field in declaration order] as compiled; returns the number of entries. */
+int32_t smrt_sar_abi(int32_t* out, int32_t capacity);
+
 #if defined(__GNUC__)
 #pragma GCC visibility pop
 #endif

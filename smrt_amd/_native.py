@@ -475,6 +475,109 @@ class LrmOutput:
                 _dptr(self.vertical))
 
 
+class SarParams(C.Structure):
+    """struct smrt_sar_params of include/smrt_dort.h."""
+    _fields_ = [(name, C.c_double) for name in (
+        "altitude", "pulse_bandwidth", "nominal_gate", "pulse_repetition_frequency", "wavelength", "velocity", "alpha", "pitch_angle",
+        "roll_angle", "sigma_p", "theta_lim", "gamma_x", "gamma_y", "l_gamma", "lz", "pu", "nu_coherent")] + [(name, C.c_int32) for name in (
+            "ngate", "ndoppler", "oversampling_time", "oversampling_doppler", "return_oversampled", "n_rows", "n_tables", "reserved")] + [
+        ("table_sigma", C.POINTER(C.c_double)), ("table_index", C.POINTER(C.c_int32)), ("boundary_values", C.POINTER(C.c_double)),
+        ("row_map", C.POINTER(C.c_int32))]
+
+
+# (sigma_g, A_g) of the Gaussian that stands for the point target response, by "<approximation>:<Doppler window>"
+# (smrt/rtsolver/delay_doppler_model/delay_doppler_utils.py: MacArthur 1976, 1978; Brown 1977; Ray et al. 2015; Dinardo et al. 2018;
+# the least-squares fits made for SMRT)
+PTR_GAUSSIAN_APPROXIMATION = {
+    "gaussian-macarthur76:rect": (0.443, 1.0), "gaussian-macarthur78:rect": (0.513, 1.0), "gaussian-brown77:rect": (0.425, 1.0),
+    "gaussian-ray15:hamming": (0.5408, 1.0055), "gaussian-dinardo18:hamming": (0.55, 1.0),
+    "gaussian-smrt:hamming": (0.54973121, 1.00758253), "gaussian-smrt:rect": (0.36018704, 1.01917462), "gaussian-smrt-test:rect": (0.1, 1),
+}
+
+
+def ptr_gaussian_approximation(ptr, window):
+    key = ptr if ":" in ptr else None if window is None else ptr + ":" + window
+    if key is None:
+        raise SMRTError("doppler_window must be set to use this DDM model. Can be 'rect', 'hamming', or ...")
+    if key not in PTR_GAUSSIAN_APPROXIMATION:
+        raise SMRTError(f"no Gaussian approximation of the point target response is known as '{key}'")
+    return PTR_GAUSSIAN_APPROXIMATION[key]
+
+
+class PackedSarParams:
+    """What one group of the nadir SAR altimetry solver shares beyond its PackedBatch (include/smrt_dort.h: smrt_sar_params): the
+    constants of Dinardo et al. 2018 for `sensor` (an Altimeter, one frequency), the distinct sigma_surface of the group
+    (table_sigma) with the index of every snowpack into them, boundary_values [S][Lmax + 1][4] and row_map [S][2 (Lmax + 1) + 2]."""
+
+    def __init__(self, sensor, table_sigma, table_index, boundary_values, row_map, n_rows=1, oversampling_time=4, oversampling_doppler=4,
+                 return_oversampled=False, ptr_doppler="gaussian-smrt"):
+        from .core.globalconstants import C_SPEED
+
+        s = SarParams()
+        f, h, B = float(sensor.frequency), float(sensor.altitude), float(sensor.pulse_bandwidth)
+        prf, velocity, alpha, ndoppler = float(sensor.pulse_repetition_frequency), float(sensor.velocity), float(sensor.alpha), int(sensor.ndoppler)
+        wavelength = C_SPEED / f
+        sigma_g, a_g = ptr_gaussian_approximation(ptr_doppler, sensor.doppler_window)
+        lx = (C_SPEED * h * prf) / (2 * velocity * ndoppler * f)            # R15 eq. 14, along track
+        ly = np.sqrt(C_SPEED * h / (alpha * B))                              # R15 eq. 21, across track
+        lz = C_SPEED / (2 * B)
+        gamma_x = 8 * np.log(2) / np.deg2rad(sensor.beamwidth_alongtrack) ** 2     # D18 eq. 27
+        gamma_y = 8 * np.log(2) / np.deg2rad(sensor.beamwidth_acrosstrack) ** 2
+        k = (float(sensor.antenna_gain) * wavelength * ndoppler) ** 2 * lx * ly / (4 * np.pi * h ** 4) * np.sqrt(2 * np.pi) * a_g ** 2 * sigma_g ** 2
+        beta0 = np.sqrt(C_SPEED / (B * h)) * np.sqrt(2)
+        beta12 = 1 / (2 * np.pi / wavelength * h * beta0) ** 2 + beta0 ** 2 / 4
+        s.altitude, s.pulse_bandwidth, s.nominal_gate, s.pulse_repetition_frequency = h, B, float(sensor.nominal_gate), prf
+        s.wavelength, s.velocity, s.alpha = wavelength, velocity, alpha
+        s.pitch_angle, s.roll_angle = float(sensor.pitch_angle), float(sensor.roll_angle)
+        s.sigma_p, s.theta_lim = sigma_g / B, lz / (alpha * lx)                 # D18 eq. 18
+        s.gamma_x, s.gamma_y, s.l_gamma, s.lz = gamma_x, gamma_y, alpha * h / (2 * gamma_y), lz
+        s.pu = k / np.sqrt(B) * np.sqrt(2)                                     # R15 eq. 37
+        s.nu_coherent = 1 / beta12
+        s.ngate, s.ndoppler = int(sensor.ngate), ndoppler
+        s.oversampling_time, s.oversampling_doppler = int(oversampling_time), int(oversampling_doppler)
+        s.return_oversampled, s.n_rows = int(bool(return_oversampled)), int(n_rows)
+        self.table_sigma = np.ascontiguousarray(np.atleast_1d(table_sigma), dtype=np.float64)
+        self.table_index = np.ascontiguousarray(table_index, dtype=np.int32)
+        self.boundary_values = np.ascontiguousarray(boundary_values, dtype=np.float64)
+        self.row_map = np.ascontiguousarray(row_map, dtype=np.int32)
+        s.n_tables = len(self.table_sigma)
+        s.table_sigma, s.boundary_values = _dptr(self.table_sigma), _dptr(self.boundary_values)
+        s.table_index = self.table_index.ctypes.data_as(C.POINTER(C.c_int32))
+        s.row_map = self.row_map.ctypes.data_as(C.POINTER(C.c_int32))
+        self.struct = s
+
+    @property
+    def n_sub(self):
+        return self.struct.ngate * self.struct.oversampling_time
+
+    @property
+    def shape(self):
+        """(rows, delays, Doppler frequencies) of the map of one pair."""
+        s = self.struct
+        if s.return_oversampled:
+            return s.n_rows, s.ngate * s.oversampling_time, s.ndoppler * s.oversampling_doppler
+        return s.n_rows, s.ngate, s.ndoppler
+
+
+class SarOutput:
+    """Outputs of the nadir SAR altimetry solver for `pair_count` pairs: values [rows][delays][Doppler], status, z_gate [delays],
+    layers [Lmax][5] as the LRM solver's, vertical [ngate x oversampling_time] the volume backscatter per sub-gate, echo
+    [Lmax + 1][4] per boundary (two-way travel time, attenuated coherent and incoherent echo, shift in samples)."""
+
+    def __init__(self, batch, params, pair_count):
+        Lmax = int(batch.struct.n_layers_max)
+        self.values = np.empty((pair_count,) + params.shape)
+        self.status = np.empty(pair_count, dtype=np.int32)
+        self.z_gate = np.empty((pair_count, params.shape[1]))
+        self.layers = np.empty((pair_count, Lmax, 5))
+        self.vertical = np.empty((pair_count, params.n_sub))
+        self.echo = np.empty((pair_count, Lmax + 1, 4))
+
+    def pointers(self):
+        return (_dptr(self.values), self.status.ctypes.data_as(C.POINTER(C.c_int32)), _dptr(self.z_gate), _dptr(self.layers),
+                _dptr(self.vertical), _dptr(self.echo))
+
+
 _lib = None
 
 
@@ -660,6 +763,18 @@ def load_library():
     lib.smrt_lrm_abi.argtypes = [P(C.c_int32), C.c_int32]
     for name in ("out_stride", "run_pairs", "upload_pairs", "launch", "sync", "layers", "download", "kernel_ms", "abi"):
         getattr(lib, "smrt_lrm_" + name).restype = C.c_int32
+    sar_out = [P(C.c_double), P(C.c_int32), P(C.c_double), P(C.c_double), P(C.c_double), P(C.c_double)]
+    sar_in = [C.c_void_p, P(SmrtBatch), P(SarParams), P(C.c_int64), C.c_int64]
+    lib.smrt_sar_out_stride.argtypes = [P(SarParams)]
+    lib.smrt_sar_run_pairs.argtypes = sar_in + sar_out
+    lib.smrt_sar_upload_pairs.argtypes = sar_in
+    lib.smrt_sar_launch.argtypes = [C.c_void_p]
+    lib.smrt_sar_sync.argtypes = [C.c_void_p]
+    lib.smrt_sar_download.argtypes = [C.c_void_p] + sar_out
+    lib.smrt_sar_kernel_ms.argtypes = [C.c_void_p, P(C.c_double)]
+    lib.smrt_sar_abi.argtypes = [P(C.c_int32), C.c_int32]
+    for name in ("out_stride", "run_pairs", "upload_pairs", "launch", "sync", "download", "kernel_ms", "abi"):
+        getattr(lib, "smrt_sar_" + name).restype = C.c_int32
     check_struct_layout(lib)
     _lib = lib
     return lib
@@ -693,6 +808,23 @@ def check_struct_layout(lib):
     if mine != theirs:
         raise SMRTError(f"smrt_lrm_params layout mismatch between smrt_amd/_native.py {mine} and {LIB_PATH} {theirs}: "
                         "rebuild the library or update the binding (include/smrt_dort.h)")
+    mine, theirs = sar_params_layout(), sar_abi_layout(lib)
+    if mine != theirs:
+        raise SMRTError(f"smrt_sar_params layout mismatch between smrt_amd/_native.py {mine} and {LIB_PATH} {theirs}: "
+                        "rebuild the library or update the binding (include/smrt_dort.h)")
+
+
+def sar_params_layout():
+    """[sizeof, field offsets] of the ctypes declaration of smrt_sar_params."""
+    return [C.sizeof(SarParams)] + [getattr(SarParams, name).offset for name, _ in SarParams._fields_]
+
+
+def sar_abi_layout(lib):
+    """The same as the library was compiled (smrt_sar_abi)."""
+    n = lib.smrt_sar_abi(None, 0)
+    a = (C.c_int32 * n)()
+    lib.smrt_sar_abi(a, n)
+    return list(a)
 
 
 def lrm_params_layout():
@@ -754,6 +886,8 @@ EXPORTED_SYMBOLS = [
     "smrt_multifresnel_sync", "smrt_multifresnel_download", "smrt_multifresnel_kernel_ms",
     "smrt_lrm_out_stride", "smrt_lrm_run_pairs", "smrt_lrm_upload_pairs", "smrt_lrm_launch", "smrt_lrm_sync", "smrt_lrm_download",
     "smrt_lrm_kernel_ms", "smrt_lrm_abi", "smrt_lrm_layers",
+    "smrt_sar_out_stride", "smrt_sar_run_pairs", "smrt_sar_upload_pairs", "smrt_sar_launch", "smrt_sar_sync", "smrt_sar_download",
+    "smrt_sar_kernel_ms", "smrt_sar_abi",
 ]
 
 
@@ -1119,6 +1253,28 @@ class DortContext:
     def lrm_kernel_ms(self):
         """HIP-event ms of the three kernels of the last launch: layer scalars, vertical distribution, waveform."""
         return self._solver_kernel_ms("lrm", 3)
+
+    # ---- the nadir SAR altimetry solver (smrt_sar_*) ----------------------------------------------------------------
+    def sar_run(self, batch: PackedBatch, params, pairs=None) -> SarOutput:
+        """One shot (H2D, four kernels, D2H) for every pair of the batch or the listed ones (row i = pairs[i])."""
+        return self._solver_run("sar", SarOutput, *self._lrm_pack(batch, params, pairs))
+
+    def sar_upload(self, batch: PackedBatch, params, pairs=None):
+        """Split form (upload once, launch any number of times, sync, download); see first_order_upload for the lock."""
+        self._solver_upload("sar", *self._lrm_pack(batch, params, pairs))
+
+    def sar_launch(self):
+        self._solver_call("smrt_sar_launch")
+
+    def sar_sync(self):
+        self._solver_call("smrt_sar_sync")
+
+    def sar_download(self) -> SarOutput:
+        return self._solver_download("sar", SarOutput)
+
+    def sar_kernel_ms(self):
+        """HIP-event ms of the four kernels of the last launch: layer scalars, vertical distribution and echoes, tables, map."""
+        return self._solver_kernel_ms("sar", 4)
 
     def ft_even_phase(self, emmodel, microstructure, frequency, frac_volume, temperature, p1, p2, mu_s, mu_i, m_max, npol):
         """Azimuthal modes of the phase matrix of one layer: array [npol, npol, m_max + 1, len(mu_s), len(mu_i)]."""

@@ -236,7 +236,7 @@ def adopt_snowpack(snowpack, memo=None):
                        substrate=shared(getattr(snowpack, "substrate", None), adopt_substrate),
                        atmosphere=shared(getattr(snowpack, "atmosphere", None), adopt_atmosphere))
     adopted.source = snowpack
-    for name in ("sigma_surface", "surface_slope"):   # what the altimetry solver reads of a snowpack
+    for name in ("sigma_surface", "surface_slope", "terrain_info"):   # what the altimetry solvers read of a snowpack
         if hasattr(snowpack, name):
             setattr(adopted, name, getattr(snowpack, name))
     memo[key] = adopted

@@ -73,6 +73,12 @@ class LabeledArray:
     def rename(self, name):
         return LabeledArray(self.values, list(self.coords.items()), name=name, attrs=self.attrs)
 
+    def sum(self, dim):
+        """The sum along the dimension `dim`, which is dropped."""
+        axis = self.dims.index(dim)
+        keep = [(k, v) for k, v in self.coords.items() if k != dim]
+        return LabeledArray(self.values.sum(axis=axis), keep, name=self.name, attrs=self.attrs)
+
     def squeeze(self):
         keep = [(k, v) for k, v in self.coords.items() if len(v) != 1]
         return LabeledArray(self.values.reshape([len(v) for _, v in keep]), keep, name=self.name, attrs=self.attrs)
@@ -445,7 +451,9 @@ class ActiveResult(Result):
 class AltimetryResult(ActiveResult):
     """The waveform of an altimeter (smrt/core/result.py: AltimetryResult): dimensions (delay, theta_inc, theta), `contribution`
     in front with return_contributions.  `gate` is the gate number of every delay, `z_gate` the depth of every gate in the
-    snowpack (NaN below it), with the batch dimensions of the result in front."""
+    snowpack (NaN below it), with the batch dimensions of the result in front.  A SAR altimeter's result is a delay-Doppler map:
+    the dimension `doppler_frequency` follows `delay`, `doppler_bin` is the Doppler beam number of every frequency, and
+    `waveform()` is the sum over the Doppler frequencies."""
 
     def __init__(self, *args, z_gate=None, **kwargs):
         super().__init__(*args, **kwargs)
@@ -457,6 +465,11 @@ class AltimetryResult(ActiveResult):
     def gate(self):
         a = self.data.attrs
         return self.data.coords["delay"] * a["pulse_bandwidth"] + a["nominal_gate"]
+
+    @property
+    def doppler_bin(self):
+        a = self.data.attrs
+        return self.data.coords["doppler_frequency"] / a["pulse_repetition_frequency"] * a["ndoppler"]
 
     def save(self, filename, netcdf_engine=None):
         z_gate = self.__dict__.get("z_gate")
@@ -473,7 +486,8 @@ class AltimetryResult(ActiveResult):
             del kwargs["contribution"]
         elif "contribution" not in kwargs and "contribution" in self.data.dims:
             kwargs["contribution"] = "total"
-        return self.sigma(name=name, **kwargs)
+        wf = self.sigma(name=name, **kwargs)
+        return wf.sum("doppler_frequency") if "doppler_frequency" in wf.dims else wf
 
     def contributions(self):
         return self.data.coords["contribution"]

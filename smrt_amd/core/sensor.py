@@ -183,8 +183,8 @@ class SensorList(SensorBase):
 
 
 class Altimeter(Sensor):
-    """A low-rate-mode radar altimeter (smrt/core/sensor.py: Altimeter).  Prefer `lrm_altimeter()` or the catalogue in
-    smrt_amd.inputs.lrm_altimeter_list.  Angles of the beam widths, pitch and roll in degrees; pitch_angle, roll_angle and
+    """A radar altimeter in low-rate or SAR mode (smrt/core/sensor.py: Altimeter).  Prefer `lrm_altimeter()`, `sar_altimeter()`
+    or the catalogues in smrt_amd.inputs.lrm_altimeter_list and sar_altimeter_list.  Angles of the beam widths, pitch and roll in degrees; pitch_angle, roll_angle and
     off_nadir_angle are in radians."""
 
     def __init__(self, frequency, altitude, pulse_bandwidth, beamwidth_alongtrack, beamwidth_acrosstrack,
@@ -216,6 +216,14 @@ class Altimeter(Sensor):
 
 def lrm_altimeter(channel=None, **kwargs):
     """A generic LRM altimeter: the arguments of `Altimeter` by keyword."""
+    sensor = Altimeter(channel=channel, **kwargs)
+    sensor.basic_checks()
+    return sensor
+
+
+def sar_altimeter(channel=None, **kwargs):
+    """A generic SAR altimeter: the arguments of `Altimeter` by keyword (ndoppler, velocity and pulse_repetition_frequency
+    among them)."""
     sensor = Altimeter(channel=channel, **kwargs)
     sensor.basic_checks()
     return sensor

@@ -18,7 +18,7 @@ def substrate_kind(substrate):
 
 
 class Snowpack:
-    def __init__(self, layers=None, interfaces=None, substrate=None, atmosphere=None):
+    def __init__(self, layers=None, interfaces=None, substrate=None, atmosphere=None, terrain_info=None):
         if substrate is not None and substrate_kind(substrate) is None:
             raise SMRTError("smrt_amd implements the Flat and Reflector substrates (smrt_amd.substrate); any other substrate "
                             "must speak the reference's protocol (specular_reflection_matrix, and "
@@ -37,11 +37,13 @@ class Snowpack:
         self._facts = None
         self.substrate = substrate
         self.atmosphere = atmosphere
+        self.terrain_info = terrain_info   # core/terrain.py: TerrainInfo (the nadir_sar_altimetry solver reads it)
 
     def __add__(self, other):
         """snowpack + substrate (smrt/core/snowpack.py:__add__)."""
         if substrate_kind(other) is not None:
-            return Snowpack(layers=self.layers, interfaces=self.interfaces, substrate=other, atmosphere=self.atmosphere)
+            return Snowpack(layers=self.layers, interfaces=self.interfaces, substrate=other, atmosphere=self.atmosphere,
+                            terrain_info=self.terrain_info)
         raise SMRTError("only a substrate can be added to a snowpack in smrt_amd")
 
     @property

@@ -84,7 +84,7 @@ struct smrt_dort_ctx {
     void* comm = nullptr;
     int comm_world = 0, comm_rank = 0;
     DevBuf d_gather_out, d_gather_status, d_scalar;
-    // the solvers beside DORT (first_order.hip, ..., nadir_lrm_altimetry.hip): each its own buffers and resident batch, made
+    // the solvers beside DORT (first_order.hip, ..., nadir_sar_altimetry.hip): each its own buffers and resident batch, made
     // on first use (solver_host.hpp); orders 0 and 1 of the second-order solver are `first_order`'s
     struct FirstOrderState* first_order = nullptr;
     struct SuccessiveOrderState* successive_order = nullptr;
@@ -92,6 +92,7 @@ struct smrt_dort_ctx {
     struct MultiFresnelState* multifresnel = nullptr;
     struct SecondOrderState* second_order = nullptr;
     struct LrmState* lrm = nullptr;
+    struct SarState* sar = nullptr;
 };
 
 #ifndef SMRT_JACOBI_NT
@@ -143,6 +144,7 @@ void successive_order_active_release(smrt_dort_ctx* ctx);
 void multifresnel_release(smrt_dort_ctx* ctx);
 void second_order_release(smrt_dort_ctx* ctx);
 void lrm_release(smrt_dort_ctx* ctx);
+void sar_release(smrt_dort_ctx* ctx);
 // first_order.hip: the resident batch of the first-order solver as its kernels get it (null: nothing uploaded); the
 // second-order solver sets its carry pointer and reads the staging rows and outputs
 smrt::FoBatch* first_order_resident(smrt_dort_ctx* ctx);

@@ -209,6 +209,7 @@ void smrt_dort_destroy(smrt_dort_ctx* ctx) {
     smrt_launch::successive_order_active_release(ctx);
     smrt_launch::multifresnel_release(ctx);
     smrt_launch::lrm_release(ctx);
+    smrt_launch::sar_release(ctx);
     smrt_launch::second_order_release(ctx);
     if (ctx->ev0) (void)hipEventDestroy(ctx->ev0);
     if (ctx->ev1) (void)hipEventDestroy(ctx->ev1);

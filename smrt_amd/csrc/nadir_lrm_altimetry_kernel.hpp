@@ -30,7 +30,8 @@ struct LrmBatch {
     FoBatch fo;                     // what first_order_layer_item reads and writes (stage, layer_out); n_theta unused
     int ngate, os, n_mu, shift;     // shift: sub-gates of the nominal gate (fast path)
     int contributions, oversampled, skip_pfs, N;   // N = ngate * os
-    int rows, out_rows, n_out, pad; // rows of the vertical distribution; rows and samples per row of the waveform
+    int rows, out_rows, n_out, sar; // rows of the vertical distribution; rows and samples per row of the waveform; sar: the
+                                    // variant of nadir_sar_altimetry_kernel.hpp (0 in this solver)
     double altitude, bandwidth, gain, gamma, off_nadir, nominal_gate, pulse_sigma;
     const double* t_inc;            // [n_mu]
     const double *sigma_surface, *surface_slope;   // [S] or null
@@ -145,7 +146,10 @@ SMRT_DEV void lrm_vertical_pair(const LrmBatch& b, long long i, const LrmLane& l
     double* pre = b.prefix + i * LRM_PREFIX_ROWS * (Lmax + 1);
     double* vsd = b.vsd + i * b.rows * N;
     double* zg = b.z_gate + i * b.n_out;
-    const double* itf = b.itf ? b.itf + gp * (Lmax + 1) * (1 + b.n_mu) : nullptr;
+    // (the SAR variant: four doubles per boundary of which only the transmission is read here, no echo in the rows, the speed
+    // of a layer from its complex permittivity, the first gate at 1e-25 m)
+    const int itf_stride = b.sar ? 4 : 1 + b.n_mu;
+    const double* itf = b.itf ? b.itf + gp * (Lmax + 1) * itf_stride : nullptr;
     const double step = b.bandwidth * b.os;     // sub-gates per second
 
     int bad = 0;
@@ -168,8 +172,8 @@ SMRT_DEV void lrm_vertical_pair(const LrmBatch& b, long long i, const LrmLane& l
             if (k >= 1 && k <= L) {
                 const double e2 = fo_stage(b.fo, FO_EPS_RE, k - 1, i), e1 = k >= 2 ? fo_stage(b.fo, FO_EPS_RE, k - 2, i) : 1.0;
                 dz = fo_stage(b.fo, FO_THICK, k - 1, i);
-                dt = dz / (kCSpeed / sqrt(e2));
-                double t1 = itf ? itf[(k - 1) * (1 + b.n_mu)] : NAN;
+                dt = dz / (kCSpeed / (b.sar ? csqrt_(cmk(e2, fo_stage(b.fo, FO_EPS_IM, k - 1, i))).re : sqrt(e2)));
+                double t1 = itf ? itf[(k - 1) * itf_stride] : NAN;
                 if (t1 == -1.0) t1 = 1.0;
                 else if (!(t1 == t1)) { double rv, rh; fresnel_RvRh(cmk(e1, 0.0), cmk(e2, 0.0), 1.0, &rv, &rh); t1 = 1.0 - rv; }
                 tt = t1 * t1;
@@ -192,7 +196,8 @@ SMRT_DEV void lrm_vertical_pair(const LrmBatch& b, long long i, const LrmLane& l
         if (g < G) {
             int j;
             z = lrm_gate_depth(p, L, (double)g / step, &j);
-            if (has_last && g == G - 1) { int jj; z += 0.01 * (z - lrm_gate_depth(p, L, (double)(g - 1) / step, &jj)); }
+            if (b.sar && g == 0) z = 1e-25;
+            if (has_last && g == G - 1) { int jj; z += 0.01 * (z - (b.sar && g == 1 ? 1e-25 : lrm_gate_depth(p, L, (double)(g - 1) / step, &jj))); }
             int nb = j + 1 > L + 1 ? L + 1 : j + 1;      // boundaries at or above the gate: a boundary precedes a gate at equal depth
             while (nb <= L && p.z[nb] <= z) ++nb;
             while (nb > 0 && p.z[nb - 1] > z) --nb;
@@ -246,7 +251,7 @@ SMRT_DEV void lrm_vertical_pair(const LrmBatch& b, long long i, const LrmLane& l
                     const double dtau = 2.0 * ke * (zs[k] - zs[q]);
                     v = (1.0 - exp(-dtau)) / (2.0 * ke) * b.bs[(long long)lay * np + i] * (exp(-tauv[q]) * p.ct[c]);
                 }
-                if (want_itf && gidx[k] < 0 && itf && !(split && k == 0)) {
+                if (want_itf && !b.sar && gidx[k] < 0 && itf && !(split && k == 0)) {
                     const int bd = -1 - gidx[k];
                     const double e = bd <= L ? itf[bd * (1 + b.n_mu) + 1 + m] : 0.0;
                     if (e != 0.0) v += e * exp(-tauv[k]) * (k == 0 ? 1.0 : p.ct[cnt[k - 1] < L ? cnt[k - 1] : L]);

@@ -1,0 +1,209 @@
+// The nadir SAR altimetry solver of libsmrt_dort.so (include/smrt_dort.h: smrt_sar_*): its four kernels -- one lane per
+// (pair, layer) for the layer scalars, one workgroup per pair for the vertical distribution and the echo of the boundaries, one
+// lane per sample of the f0 / f1 tables, one workgroup per (pair, coarse Doppler bin) for the map; arithmetic in
+// nadir_sar_altimetry_kernel.hpp -- and the host side: buffers on the DORT context, upload / launch / sync / download and the
+// one-shot call.
+#include <hip/hip_runtime.h>
+#include <cmath>
+#include <cstddef>
+#include <string>
+
+#include "nadir_sar_altimetry_kernel.hpp"
+#include "solver_host.hpp"
+#include "solver_refusals.hpp"
+
+using namespace smrt;
+
+__global__ void __launch_bounds__(kSarThreads) sar_layers_kernel(SarBatch b) {
+    const long long idx = (long long)blockIdx.x * kSarThreads + threadIdx.x;
+    if (idx >= b.lrm.fo.n_pairs * b.lrm.fo.Lmax) return;
+    lrm_layer_item(b.lrm, idx % b.lrm.fo.n_pairs, (int)(idx / b.lrm.fo.n_pairs));
+}
+
+__global__ void __launch_bounds__(kSarThreads) sar_vertical_kernel(SarBatch b) {
+    extern __shared__ double sar_vertical_lds[];
+    __shared__ double wsum[kSarThreads / 64];
+    LrmLane ln;
+    ln.tid = threadIdx.x; ln.nt = kSarThreads; ln.wsum = wsum;
+    lrm_vertical_pair(b.lrm, blockIdx.x, ln, (unsigned char*)sar_vertical_lds);
+    lrm_sync();
+    sar_boundary_pair(b, blockIdx.x, threadIdx.x, kSarThreads);
+}
+
+__global__ void __launch_bounds__(kSarThreads) sar_tables_kernel(SarBatch b) {
+    const long long idx = (long long)blockIdx.x * kSarThreads + threadIdx.x;
+    if (idx >= (long long)b.n_tab * b.lrm.N * b.ND) return;
+    sar_table_item(b, idx);
+}
+
+__global__ void __launch_bounds__(kSarThreads) sar_combine_kernel(SarBatch b) {
+    extern __shared__ double sar_combine_lds[];
+    sar_combine_item(b, blockIdx.x / b.ndoppler, (int)(blockIdx.x % b.ndoppler), threadIdx.x, kSarThreads, (unsigned char*)sar_combine_lds);
+}
+
+struct SarState : solver_host::InputState {
+    DevBuf &hostlayer = buf(), &hostcoeff = buf(), &tabsigma = buf(), &tabindex = buf(), &bv = buf(), &rowmap = buf();
+    DevBuf &stage = buf(), &bs = buf(), &prefix = buf(), &vsd = buf(), &zgate = buf(), &status = buf(), &layer = buf();
+    DevBuf &tables = buf(), &echo = buf(), &out = buf();
+    SarBatch dev{};
+    size_t lds_vertical = 0, lds_combine = 0;
+    bool uploaded = false;
+    bool timed = false;   // events 0 .. 4 around the four kernels of the last launch
+};
+
+namespace smrt_launch {
+void sar_release(smrt_dort_ctx* ctx) { solver_host::release(ctx->sar); }
+}  // namespace smrt_launch
+
+extern "C" {
+
+int32_t smrt_sar_out_stride(const smrt_sar_params* p) {
+    if (!p || p->ngate < 1 || p->ndoppler < 1 || p->oversampling_time < 1 || p->oversampling_doppler < 1 || p->n_rows < 1) return -1;
+    const long long n = (long long)p->n_rows * p->ngate * p->ndoppler * (p->return_oversampled ? p->oversampling_time * p->oversampling_doppler : 1);
+    return n > 0x7fffffffLL ? -1 : (int32_t)n;
+}
+
+int32_t smrt_sar_abi(int32_t* out, int32_t capacity) {
+#define SMRT_OFF(f) (int32_t)offsetof(smrt_sar_params, f)
+    const int32_t desc[] = {(int32_t)sizeof(smrt_sar_params), SMRT_OFF(altitude), SMRT_OFF(pulse_bandwidth), SMRT_OFF(nominal_gate),
+                            SMRT_OFF(pulse_repetition_frequency), SMRT_OFF(wavelength), SMRT_OFF(velocity), SMRT_OFF(alpha),
+                            SMRT_OFF(pitch_angle), SMRT_OFF(roll_angle), SMRT_OFF(sigma_p), SMRT_OFF(theta_lim), SMRT_OFF(gamma_x),
+                            SMRT_OFF(gamma_y), SMRT_OFF(l_gamma), SMRT_OFF(lz), SMRT_OFF(pu), SMRT_OFF(nu_coherent), SMRT_OFF(ngate),
+                            SMRT_OFF(ndoppler), SMRT_OFF(oversampling_time), SMRT_OFF(oversampling_doppler), SMRT_OFF(return_oversampled),
+                            SMRT_OFF(n_rows), SMRT_OFF(n_tables), SMRT_OFF(reserved), SMRT_OFF(table_sigma), SMRT_OFF(table_index),
+                            SMRT_OFF(boundary_values), SMRT_OFF(row_map)};
+#undef SMRT_OFF
+    return solver_host::copy_table(desc, out, capacity);
+}
+
+int32_t smrt_sar_upload_pairs(smrt_dort_ctx* ctx, const smrt_batch* b, const smrt_sar_params* p, const int64_t* pairs, int64_t n_pairs) {
+    if (!ctx) return -1;
+    const char* why = solver_refusals::nadir_sar_altimetry(b, p);
+    if (why) { ctx->err = why; return -1; }
+    if (solver_host::check_pairs(ctx, pairs, &n_pairs, (int64_t)b->n_snowpacks)) return -1;
+    const size_t S = b->n_snowpacks, L = b->n_layers_max, NP = (size_t)n_pairs;
+    const size_t stride = (size_t)smrt_sar_out_stride(p);
+    if (NP * stride * sizeof(double) > solver_refusals::kSarOutputBudget) {
+        ctx->err = "the maps of these pairs do not fit the output budget of the nadir SAR altimetry solver: launch fewer pairs at a time";
+        return -1;
+    }
+    HIPCHK(hipSetDevice(ctx->device));
+    if (!ctx->sar) ctx->sar = new SarState();
+    SarState* st = ctx->sar;
+    st->uploaded = false;
+    const size_t SL = S * L;
+    SarBatch d{};
+    LrmBatch& lb = d.lrm;
+    FoBatch& fo = lb.fo;
+    fo.S = (int)S; fo.Lmax = (int)L; fo.F = 1; fo.n_theta = 1;
+    fo.emmodel = b->emmodel; fo.micro = b->microstructure; fo.sub_kind = 0; fo.n_slots = 0;
+    fo.n_pairs = n_pairs;
+    lb.ngate = p->ngate; lb.os = p->oversampling_time; lb.n_mu = 1; lb.shift = 0;
+    lb.contributions = 0; lb.oversampled = p->return_oversampled ? 1 : 0; lb.skip_pfs = 0;
+    lb.N = p->ngate * p->oversampling_time;
+    lb.rows = 1; lb.out_rows = 1; lb.n_out = lb.oversampled ? lb.N : lb.ngate; lb.sar = 1;
+    lb.altitude = p->altitude; lb.bandwidth = p->pulse_bandwidth; lb.nominal_gate = p->nominal_gate;
+    d.ndoppler = p->ndoppler; d.osd = p->oversampling_doppler; d.ND = p->ndoppler * p->oversampling_doppler;
+    d.out_rows = p->n_rows; d.n_tab = p->n_tables;
+    d.n_t = lb.n_out; d.n_d = lb.oversampled ? d.ND : d.ndoppler;
+    d.prf = p->pulse_repetition_frequency; d.wavelength = p->wavelength; d.velocity = p->velocity; d.alpha = p->alpha;
+    d.pitch = p->pitch_angle; d.roll = p->roll_angle; d.sigma_p = p->sigma_p; d.theta_lim = p->theta_lim;
+    d.gamma_x = p->gamma_x; d.gamma_y = p->gamma_y; d.l_gamma = p->l_gamma; d.lz = p->lz; d.pu = p->pu; d.nu_coherent = p->nu_coherent;
+    using solver_host::upload;
+    if (solver_host::upload_batch(ctx, st, b, pairs, fo)) return -1;   // (fo.sub_kind is none: the substrate is not read)
+    if (b->host_layer && upload(ctx, st->hostlayer, b->host_layer, SL * 4 * sizeof(double), fo.host_layer)) return -1;
+    if (b->host_iba_coeff && upload(ctx, st->hostcoeff, b->host_iba_coeff, SL * sizeof(double), fo.host_coeff)) return -1;
+    if (upload(ctx, st->tabsigma, p->table_sigma, p->n_tables * sizeof(double), d.tab_sigma)) return -1;
+    if (upload(ctx, st->tabindex, p->table_index, S * sizeof(int32_t), d.tab_index)) return -1;
+    if (upload(ctx, st->bv, p->boundary_values, S * (L + 1) * SAR_BV * sizeof(double), lb.itf)) return -1;
+    if (upload(ctx, st->rowmap, p->row_map, S * (2 * (L + 1) + 2) * sizeof(int32_t), d.row_map)) return -1;
+    HIPCHK(st->stage.reserve((size_t)FO_ROWS * L * NP * sizeof(double)));
+    HIPCHK(st->bs.reserve(L * NP * sizeof(double)));
+    HIPCHK(st->prefix.reserve(NP * LRM_PREFIX_ROWS * (L + 1) * sizeof(double)));
+    HIPCHK(st->vsd.reserve(NP * lb.N * sizeof(double)));
+    HIPCHK(st->zgate.reserve(NP * lb.n_out * sizeof(double)));
+    HIPCHK(st->status.reserve(NP * sizeof(int32_t)));
+    HIPCHK(st->layer.reserve(NP * L * 5 * sizeof(double)));
+    HIPCHK(st->tables.reserve((size_t)p->n_tables * 2 * lb.N * d.ND * sizeof(double)));
+    HIPCHK(st->echo.reserve(NP * (L + 1) * SAR_ECHO * sizeof(double)));
+    HIPCHK(st->out.reserve(NP * stride * sizeof(double)));
+    fo.stage = (double*)st->stage.p; fo.layer_out = (double*)st->layer.p;
+    lb.bs = (double*)st->bs.p; lb.prefix = (double*)st->prefix.p; lb.vsd = (double*)st->vsd.p; lb.out = nullptr;
+    lb.z_gate = (double*)st->zgate.p; lb.status = (int*)st->status.p;
+    d.tables = (double*)st->tables.p; d.echo = (double*)st->echo.p; d.out = (double*)st->out.p;
+    st->lds_vertical = lrm_vertical_lds_bytes(lb.N, (int)L);
+    st->lds_combine = sar_combine_lds_bytes(lb.N, d.osd);
+    if (solver_host::uploads_done(ctx)) return -1;
+    st->dev = d;
+    st->uploaded = true;
+    st->timed = false;
+    return 0;
+}
+
+int32_t smrt_sar_launch(smrt_dort_ctx* ctx) {
+    if (!ctx) return -1;
+    SarState* st = ctx->sar;
+    if (!st || !st->uploaded) { ctx->err = "no SAR altimetry batch uploaded"; return -1; }
+    HIPCHK(hipSetDevice(ctx->device));
+    const SarBatch& d = st->dev;
+    const long long items = d.lrm.fo.n_pairs * d.lrm.fo.Lmax, samples = (long long)d.n_tab * d.lrm.N * d.ND;
+    // (a per-function setting shared by every context of the process: set for THIS batch at every launch)
+    HIPCHK(hipFuncSetAttribute((const void*)sar_vertical_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)st->lds_vertical));
+    HIPCHK(hipFuncSetAttribute((const void*)sar_combine_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)st->lds_combine));
+    st->rewind();
+    if (solver_host::record(ctx, st)) return -1;
+    hipLaunchKernelGGL(sar_layers_kernel, dim3((unsigned)((items + kSarThreads - 1) / kSarThreads)), dim3(kSarThreads), 0, ctx->stream, d);
+    HIPCHK(hipGetLastError());
+    if (solver_host::record(ctx, st)) return -1;
+    hipLaunchKernelGGL(sar_vertical_kernel, dim3((unsigned)d.lrm.fo.n_pairs), dim3(kSarThreads), st->lds_vertical, ctx->stream, d);
+    HIPCHK(hipGetLastError());
+    if (solver_host::record(ctx, st)) return -1;
+    hipLaunchKernelGGL(sar_tables_kernel, dim3((unsigned)((samples + kSarThreads - 1) / kSarThreads)), dim3(kSarThreads), 0, ctx->stream, d);
+    HIPCHK(hipGetLastError());
+    if (solver_host::record(ctx, st)) return -1;
+    hipLaunchKernelGGL(sar_combine_kernel, dim3((unsigned)(d.lrm.fo.n_pairs * d.ndoppler)), dim3(kSarThreads), st->lds_combine, ctx->stream, d);
+    HIPCHK(hipGetLastError());
+    if (solver_host::record(ctx, st)) return -1;
+    st->timed = true;
+    return 0;
+}
+
+int32_t smrt_sar_sync(smrt_dort_ctx* ctx) { return solver_host::sync(ctx); }
+
+int32_t smrt_sar_kernel_ms(smrt_dort_ctx* ctx, double* ms4) {
+    if (!ctx || !ms4) return -1;
+    SarState* st = ctx->sar;
+    if (!st || !st->timed) { ctx->err = "no SAR altimetry launch to time"; return -1; }
+    if (solver_host::wait_recorded(ctx, st)) return -1;
+    for (int k = 0; k < 4; ++k) {
+        ms4[k] = 0.0;
+        if (solver_host::add_elapsed(ctx, st, k, k + 1, &ms4[k])) return -1;
+    }
+    return 0;
+}
+
+int32_t smrt_sar_download(smrt_dort_ctx* ctx, double* out, int32_t* status, double* z_gate, double* layer_out, double* vertical, double* echo) {
+    if (!ctx) return -1;
+    SarState* st = ctx->sar;
+    if (!st || !st->uploaded) { ctx->err = "no SAR altimetry batch uploaded"; return -1; }
+    HIPCHK(hipSetDevice(ctx->device));
+    const SarBatch& d = st->dev;
+    const size_t NP = (size_t)d.lrm.fo.n_pairs, L = d.lrm.fo.Lmax;
+    if (out) HIPCHK(hipMemcpyAsync(out, d.out, NP * d.out_rows * d.n_t * d.n_d * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    if (status) HIPCHK(hipMemcpyAsync(status, d.lrm.status, NP * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
+    if (z_gate) HIPCHK(hipMemcpyAsync(z_gate, d.lrm.z_gate, NP * d.lrm.n_out * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    if (layer_out) HIPCHK(hipMemcpyAsync(layer_out, d.lrm.fo.layer_out, NP * L * 5 * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    if (vertical) HIPCHK(hipMemcpyAsync(vertical, d.lrm.vsd, NP * d.lrm.N * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    if (echo) HIPCHK(hipMemcpyAsync(echo, d.echo, NP * (L + 1) * SAR_ECHO * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(hipStreamSynchronize(ctx->stream));
+    return 0;
+}
+
+int32_t smrt_sar_run_pairs(smrt_dort_ctx* ctx, const smrt_batch* batch, const smrt_sar_params* params, const int64_t* pairs,
+                           int64_t n_pairs, double* out, int32_t* status, double* z_gate, double* layer_out, double* vertical, double* echo) {
+    if (smrt_sar_upload_pairs(ctx, batch, params, pairs, n_pairs)) return -1;
+    if (smrt_sar_launch(ctx)) return -1;
+    return smrt_sar_download(ctx, out, status, z_gate, layer_out, vertical, echo);
+}
+
+}  // extern "C"

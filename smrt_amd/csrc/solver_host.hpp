@@ -1,5 +1,5 @@
 // Host scaffold shared by the solvers beside DORT (first_order.hip, second_order.hip, successive_order.hip,
-// successive_order_active.hip, multifresnel.hip, nadir_lrm_altimetry.hip): the error macro, the state base that owns a
+// successive_order_active.hip, multifresnel.hip, nadir_lrm_altimetry.hip, nadir_sar_altimetry.hip): the error macro, the state base that owns a
 // solver's device buffers and events, and the steps every entry point repeats -- pair list, upload of the smrt_batch
 // arrays, sync, event times, table copies.  What differs between the solvers (kernels, chunk plans, launches, downloads)
 // stays in their files; what they refuse is in solver_refusals.hpp.

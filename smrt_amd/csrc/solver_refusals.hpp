@@ -9,6 +9,7 @@
 
 #include "dort_host_common.hpp"
 #include "nadir_lrm_altimetry_kernel.hpp"   // lrm_vertical_lds_bytes, lrm_waveform_lds_bytes
+#include "nadir_sar_altimetry_kernel.hpp"   // sar_combine_lds_bytes
 #include "second_order_kernel.hpp"          // kSo2MaxModes
 #include "successive_order_kernel.hpp"      // kSoMaxStream
 
@@ -137,6 +138,41 @@ inline const char* nadir_lrm_altimetry(const smrt_batch* b, const smrt_lrm_param
     const size_t a = smrt::lrm_vertical_lds_bytes(p->ngate * p->oversampling, b->n_layers_max);
     const size_t c = smrt::lrm_waveform_lds_bytes(p->ngate * p->oversampling, p->n_mu);
     if (a > kLrmLdsLimit || c > kLrmLdsLimit) return "ngate x oversampling_time (and the layers) do not fit the local data share";
+    return nullptr;
+}
+
+constexpr size_t kSarOutputBudget = (size_t)2 << 30;   // bytes of the maps of one launch (the caller splits the pairs)
+
+inline const char* nadir_sar_altimetry(const smrt_batch* b, const smrt_sar_params* p) {
+    static const SolverAccepts accepts{false, false, 0, nullptr, nullptr, 0, nullptr, false};   // (any mode; the substrate is not read)
+    if (!b || !p) return "null batch or parameters";
+    const char* why = refuse_empty(b);
+    if (why) return why;
+    if (b->n_frequencies != 1) return "the nadir SAR altimetry solver takes one frequency per batch (the sensor constants depend on it)";
+    if (b->atm_tb_down || b->atm_tb_up || b->atm_transmittance) return "the nadir SAR altimetry solver can not handle atmosphere";
+    if (b->host_phase) return "the nadir SAR altimetry solver has no route for phase matrices evaluated on the host";
+    if (b->process_coherent_layers) return "process_coherent_layers is not available in the nadir SAR altimetry solver";
+    if ((why = refuse_inputs(b, accepts))) return why;
+    if (p->ngate < 1 || p->oversampling_time < 1 || p->oversampling_doppler < 1) return "ngate and the oversampling factors must be positive";
+    if (p->ndoppler < 2 || p->ndoppler % 2) return "ndoppler must be even and positive (the reference's Doppler axis has another length than its map otherwise)";
+    if ((long long)p->ngate * p->oversampling_time > (1 << 20) || (long long)p->ndoppler * p->oversampling_doppler > (1 << 20))
+        return "the oversampled map is too large";
+    if (!(p->altitude > 0.0) || !(p->pulse_bandwidth > 0.0) || !(p->velocity > 0.0) || !(p->pulse_repetition_frequency > 0.0) ||
+        !(p->sigma_p > 0.0) || !(p->theta_lim > 0.0) || !(p->gamma_y > 0.0) || !(p->l_gamma > 0.0) || !(p->lz > 0.0))
+        return "invalid sensor parameters";
+    if (!p->table_sigma || !p->table_index || !p->boundary_values || !p->row_map || p->n_tables < 1) return "the tables, the boundary values or the row map are missing";
+    if (p->n_rows < 1) return "n_rows must be positive";
+    for (int t = 0; t < p->n_tables; ++t)
+        if (!(p->table_sigma[t] >= 0.0)) return "sigma_surface must be non-negative";
+    const int sources = 2 * (b->n_layers_max + 1) + 2;
+    for (int s = 0; s < b->n_snowpacks; ++s) {
+        if (p->table_index[s] < 0 || p->table_index[s] >= p->n_tables) return "table_index entry out of range";
+        for (int k = 0; k < sources; ++k)
+            if (p->row_map[(long long)s * sources + k] < -1 || p->row_map[(long long)s * sources + k] >= p->n_rows) return "row_map entry out of range";
+    }
+    const size_t a = smrt::lrm_vertical_lds_bytes(p->ngate * p->oversampling_time, b->n_layers_max);
+    const size_t c = smrt::sar_combine_lds_bytes(p->ngate * p->oversampling_time, p->oversampling_doppler);
+    if (a > kLrmLdsLimit || c > kLrmLdsLimit) return "ngate x oversampling_time x oversampling_doppler (and the layers) do not fit the local data share";
     return nullptr;
 }
 

@@ -1,0 +1,238 @@
+#!/usr/bin/env python
+"""Rates of the nadir SAR altimetry solver: 128 snowpacks of 30 layers with geometrical-optics interfaces, cryosat2_sarm(), default
+options (512 x 256 oversampled samples per map, Dinardo18): 8192 workgroups of the map kernel per launch.  The batch is small
+because packing it evaluates the transmission of every geometrical-optics interface on the host (a hemispherical integral, about
+14 ms each, 0.4 s per snowpack of 30 layers): that cost is inside the Model.run rate and outside the other two.  Four steps, each a child process under its own `timeout`: the NumPy /
+SciPy restatement on the host (no GPU), then -- unless --host-only -- the resident-input rate (median of the HIP-event times of the
+four kernels over `steps` launches after `warmup`), the rate with H2D + D2H, and Model.run.  Writes
+profiles/nadir_sar_altimetry_rate.txt; a step that was not run or did not finish is recorded as "not measured"; every line names
+the processor it was measured on.  No rate is a gate.
+    python tools/bench_nadir_sar_altimetry.py [--host-only] [--out=FILE] [steps] [warmup] [snowpacks]"""
+import json
+import os
+import subprocess
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tests"))
+REFERENCE_MS = 900     # what --step reference gave where the reference is installed (one core, median of four solves, one run)
+OUT = os.path.join(ROOT, "profiles", "nadir_sar_altimetry_rate.txt")
+LAYERS = 30
+
+
+def snowpacks(n, seed=0):
+    from smrt_amd.core.terrain import TerrainInfo
+    from smrt_amd.inputs.make_medium import make_interface, make_snowpack
+
+    rng = np.random.RandomState(seed)
+    rough = [make_interface("geometrical_optics_backscatter", roughness_rms=0.005, corr_length=0.10) for _ in range(LAYERS)]
+    sps = []
+    for k in range(n):     # 0.02 to 0.2 m per layer: every interface inside the window of 128 gates
+        sp = make_snowpack(list(rng.uniform(0.02, 0.2, LAYERS)), "exponential", density=list(rng.uniform(250.0, 450.0, LAYERS)),
+                           temperature=list(rng.uniform(245.0, 265.0, LAYERS)), corr_length=list(rng.uniform(1e-4, 3e-4, LAYERS)), interface=rough)
+        sp.terrain_info = TerrainInfo(sigma_surface=0.1 + 0.1 * (k % 2))
+        sps.append(sp)
+    return sps
+
+
+def packed(n):
+    """(context, batch, parameters) of one group as Model.run packs it: the interfaces are evaluated on the host first."""
+    from smrt_amd import make_model
+    from smrt_amd.inputs import sar_altimeter_list
+    from smrt_amd.rtsolver.dort import get_context
+
+    ctx = get_context(None)
+    run, kept = ctx.sar_run, {}
+
+    def spy(batch, params, pairs=None):
+        kept.update(batch=batch, params=params)
+        return run(batch, params, pairs=pairs)
+
+    ctx.sar_run = spy
+    try:
+        make_model("iba", "nadir_sar_altimetry").run(sar_altimeter_list.cryosat2_sarm(), snowpacks(n))
+    finally:
+        del ctx.sar_run
+    return ctx, kept["batch"], kept["params"]
+
+
+def step_host(n, steps, warmup):
+    import types
+
+    from nadir_sar_altimetry_restatement import solve_case
+    from smrt_amd.core.terrain import TerrainInfo
+    from smrt_amd.inputs import sar_altimeter_list
+    from smrt_amd.inputs.make_medium import make_interface, make_snowpack, make_soil
+
+    api = types.SimpleNamespace(make_snowpack=make_snowpack, make_soil=make_soil, make_interface=make_interface,
+                                sar_altimeter_list=sar_altimeter_list, TerrainInfo=TerrainInfo)
+    rng = np.random.RandomState(0)
+    case = dict(name="bench", sensor="cryosat2_sarm", thickness=list(rng.uniform(0.02, 0.2, LAYERS)), density=list(rng.uniform(250.0, 450.0, LAYERS)),
+                temperature=list(rng.uniform(245.0, 265.0, LAYERS)), corr_length=list(rng.uniform(1e-4, 3e-4, LAYERS)),
+                interface=[dict(roughness_rms=0.005, corr_length=0.10)] * LAYERS, sigma_surface=0.2)
+    solve_case(case, api)
+    t0 = time.perf_counter()
+    for _ in range(3):
+        solve_case(case, api)
+    return dict(ms_per_solve=(time.perf_counter() - t0) / 3 * 1e3)
+
+
+def step_reference(n, steps, warmup):
+    """The reference's own NadirSARAltimetry.solve on the bench's snowpack, emmodel preparation included, where the reference
+    package is (its directory in SMRT_REFERENCE, by default next to this repository), with the stand-ins of tests/golden/_refstubs;
+    the result object is replaced by a recorder as in tests/golden/make_nadir_sar_altimetry_fixtures.py.  Median of four solves."""
+    import contextlib
+    import io
+    import types
+
+    sys.path.insert(0, os.path.join(ROOT, "tests", "golden", "_refstubs"))
+    sys.path.insert(0, os.environ.get("SMRT_REFERENCE", os.path.join(os.path.dirname(ROOT), "reference")))
+    from smrt import make_interface, make_model, make_snowpack
+    from smrt.core.terrain import TerrainInfo
+    from smrt.inputs import sar_altimeter_list
+    from smrt.rtsolver import nadir_sar_altimetry as reference
+
+    class Recorded:
+        def __init__(self, values, coords=None):
+            self.values = np.asarray(values)
+            for c in coords:
+                if isinstance(c, tuple):
+                    setattr(self, c[0], np.asarray(c[1]))
+
+        def assign_coords(self, **kwargs):
+            return self
+
+    reference.xr = types.SimpleNamespace(DataArray=Recorded)
+    reference.AltimetryResult = lambda res: res
+    rng = np.random.RandomState(0)
+    rough = [make_interface("geometrical_optics_backscatter", roughness_rms=0.005, corr_length=0.10) for _ in range(LAYERS)]
+    sp = make_snowpack(list(rng.uniform(0.02, 0.2, LAYERS)), "exponential", density=list(rng.uniform(250.0, 450.0, LAYERS)),
+                       temperature=list(rng.uniform(245.0, 265.0, LAYERS)), corr_length=list(rng.uniform(1e-4, 3e-4, LAYERS)), interface=rough)
+    sp.terrain_info = TerrainInfo(sigma_surface=0.2)
+    sensor, times = sar_altimeter_list.cryosat2_sarm(), []
+    with contextlib.redirect_stdout(io.StringIO()):   # (the reference prints from __init__ and from Dinardo18)
+        m = make_model("iba", "nadir_sar_altimetry", rtsolver_options=dict(return_oversampled=True))
+        for _ in range(4):
+            t0 = time.perf_counter()
+            emmodels = m.prepare_emmodels(sensor, sp)
+            solver = m.rtsolver(return_oversampled=True) if isinstance(m.rtsolver, type) else m.rtsolver
+            solver.solve(sp, emmodels, sensor)
+            times.append(time.perf_counter() - t0)
+    return dict(ms_per_solve=float(np.median(times)) * 1e3)
+
+
+def step_resident(n, steps, warmup):
+    ctx, batch, params = packed(n)
+    ctx.sar_upload(batch, params)
+    times = []
+    for k in range(warmup + steps):
+        ctx.sar_launch()
+        ctx.sar_sync()
+        if k >= warmup:
+            times.append(ctx.sar_kernel_ms())
+    med = np.median(np.array(times), axis=0)
+    assert np.all(ctx.sar_download().status == 0)
+    return dict(kernel_ms=[float(x) for x in med], solves_per_s=n / (med.sum() * 1e-3), spread_ms=float(np.ptp(np.array(times).sum(axis=1))))
+
+
+def step_transfers(n, steps, warmup):
+    ctx, batch, params = packed(n)
+    times = []
+    for k in range(warmup + steps):
+        t0 = time.perf_counter()
+        out = ctx.sar_run(batch, params)
+        if k >= warmup:
+            times.append(time.perf_counter() - t0)
+    assert np.all(out.status == 0)
+    return dict(solves_per_s=n / float(np.median(times)))
+
+
+def step_model(n, steps, warmup):
+    from smrt_amd import make_model
+    from smrt_amd.inputs import sar_altimeter_list
+
+    m, sensor, sps = make_model("iba", "nadir_sar_altimetry"), sar_altimeter_list.cryosat2_sarm(), snowpacks(n)
+    times = []
+    for k in range(max(1, warmup) + max(2, steps // 3)):
+        t0 = time.perf_counter()
+        res = m.run(sensor, sps)
+        if k >= max(1, warmup):
+            times.append(time.perf_counter() - t0)
+    assert np.all(np.isfinite(res.data.values))
+    return dict(solves_per_s=n / float(np.median(times)))
+
+
+STEPS = dict(reference=step_reference, host=step_host, resident=step_resident, transfers=step_transfers, model=step_model)
+
+
+def host_cpu():
+    try:
+        with open("/proc/cpuinfo") as fh:
+            return next(line.split(":", 1)[1].strip() for line in fh if line.startswith("model name"))
+    except (OSError, StopIteration):
+        import platform
+
+        return platform.processor() or platform.machine()
+
+
+def gpu_name():
+    try:
+        import torch
+
+        props = torch.cuda.get_device_properties(0)
+        return f"{props.name}, {getattr(props, 'gcnArchName', '').split(':')[0]}"
+    except Exception:
+        return "GPU 0"
+
+
+def describe(name, r):
+    """One line of the file from the JSON of a step, figures rounded to what a timing of this kind resolves."""
+    if name in ("host", "reference"):
+        return f"{r['ms_per_solve']:.1f} ms per solve ({1e3 / r['ms_per_solve']:.0f} solves/s)"
+    if name == "resident":
+        k = r["kernel_ms"]
+        return (f"{r['solves_per_s']:.3g} solves/s; kernels: layer scalars {k[0]:.2f} ms, vertical distribution and echoes {k[1]:.2f} ms, "
+                f"tables {k[2]:.2f} ms, map {k[3]:.2f} ms per launch (median), spread of the launch total {r['spread_ms']:.2f} ms")
+    return f"{r['solves_per_s']:.3g} solves/s"
+
+
+def main():
+    out_path = next((a.split("=", 1)[1] for a in sys.argv[1:] if a.startswith("--out=")), OUT)
+    args = [a for a in sys.argv[1:] if not a.startswith("--")]
+    if "--step" in sys.argv:
+        name = sys.argv[sys.argv.index("--step") + 1]
+        args = [a for a in args if a != name]
+        steps, warmup, n = (int(a) for a in args[:3])
+        print(json.dumps(STEPS[name](n, steps, warmup)))
+        return
+    steps, warmup, n = (int(a) for a in (args + ["10", "2", "128"][len(args):])[:3])
+    yardstick = f"{REFERENCE_MS} ms; re-measure with `python tools/bench_nadir_sar_altimetry.py --step reference 0 0 1`"
+    lines = ["nadir SAR altimetry solver: rates (tools/bench_nadir_sar_altimetry.py)",
+             f"batch: {n} snowpacks x {LAYERS} layers, cryosat2_sarm(), default options (Dinardo18, oversampling 4 x 4, two sigma_surface)",
+             f"yardstick: the reference per solve on one CPU core (same case, on the machine that has the reference installed): {yardstick}"]
+    for name in ("host", "resident", "transfers", "model"):
+        if name != "host" and "--host-only" in sys.argv:
+            lines.append(f"{name}: not measured")
+            continue
+        cmd = ["timeout", "-k", "10", "300", sys.executable, os.path.abspath(__file__), "--step", name, str(steps), str(warmup), str(n)]
+        proc = subprocess.run(cmd, cwd=ROOT, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True)
+        if proc.returncode != 0:
+            lines.append(f"{name}: not measured (the step ended with status {proc.returncode})")
+            if name != "host":
+                break       # nothing more is started on the GPU after a step that failed
+            continue
+        where = f"NumPy restatement, one core of {host_cpu()}" if name == "host" else gpu_name()
+        what = dict(host="host", resident="resident inputs", transfers="with H2D and D2H", model="Model.run")[name]
+        lines.append(f"{what} ({where}): {describe(name, json.loads(proc.stdout.strip().splitlines()[-1]))}")
+    os.makedirs(os.path.dirname(os.path.abspath(out_path)), exist_ok=True)
+    with open(out_path, "w") as fh:
+        fh.write("\n".join(lines) + "\n")
+    print("\n".join(lines))
+
+
+if __name__ == "__main__":
+    main()

@@ -38,6 +38,8 @@ def ctype_of(decl):
         return "C.c_void_p"
     if base == "smrt_lrm_params":   # the altimeter and options of one group (seven doubles, eight int32, four pointers): likewise
         return "C.c_void_p"
+    if base == "smrt_sar_params":   # the SAR altimeter, the model constants and options of one group (17 doubles, eight int32, four pointers): likewise
+        return "C.c_void_p"
     c = SCALARS[base]
     for _ in range(stars):
         c = "C.POINTER(%s)" % c
