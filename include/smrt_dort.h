@@ -794,7 +794,19 @@ int32_t smrt_lrm_abi(int32_t* out, int32_t capacity);
  * (may be NULL) z_gate [delays] (NaN below the snowpack), layer_out [n_layers_max][5] as the LRM solver's, vertical
  * [ngate x oversampling_time] the volume backscatter per sub-gate, echo [n_layers_max + 1][4] per boundary: two-way travel
  * time, attenuated coherent and incoherent echo, shift in samples.  The maps of one launch stay below 2 GiB: more pairs are refused.
+ *
+ * Appended for the delay-Doppler model of Halimi et al. 2014 (delay_doppler_model/halimi14.py); a caller that zero-fills the
+ * struct gets Dinardo18:
+ *   delay_doppler_model      SMRT_SAR_DINARDO18 (0) or SMRT_SAR_HALIMI14 (1); any other value is refused;
+ *   slant_range_correction   Halimi14: the delay compensation per Doppler column (0: the pseudo-LRM mode);
+ *   delay_window_widening    Halimi14: the impulse response and the convolutions are made on ngate x delay_window_widening
+ *                            gates, of which the first ngate are kept (>= 1 then; Dinardo18 reads none of the three);
+ *   h14_pu, h14_gamma, burst_duration   Halimi14: Pu x ndoppler^2 (H14 after eq. 3, in the Nb^2 convention of eq. 14), gamma
+ *                            of the mean of the two beamwidths (after eq. 3), the duration of a burst (eq. 19).
+ * With Halimi14 a group has ONE table per distinct sigma_surface and every boundary adds that table, shifted and scaled by its
+ * echoes: sigma_p ... nu_coherent and the fourth boundary value are not read.
  */
+enum { SMRT_SAR_DINARDO18 = 0, SMRT_SAR_HALIMI14 = 1 };
 typedef struct smrt_sar_params {
     double altitude;
     double pulse_bandwidth;
@@ -825,6 +837,13 @@ typedef struct smrt_sar_params {
     const int32_t* table_index;
     const double* boundary_values;
     const int32_t* row_map;
+    int32_t delay_doppler_model;
+    int32_t slant_range_correction;
+    int32_t delay_window_widening;
+    int32_t reserved2;
+    double h14_pu;
+    double h14_gamma;
+    double burst_duration;
 } smrt_sar_params;
 /* Doubles per pair of `out` (negative: invalid parameters). */
 int32_t smrt_sar_out_stride(const smrt_sar_params* p);
@@ -838,8 +857,8 @@ int32_t smrt_sar_upload_pairs(smrt_dort_ctx* ctx, const smrt_batch* batch, const
 int32_t smrt_sar_launch(smrt_dort_ctx* ctx);
 int32_t smrt_sar_sync(smrt_dort_ctx* ctx);
 int32_t smrt_sar_download(smrt_dort_ctx* ctx, double* out, int32_t* status, double* z_gate, double* layer_out, double* vertical, double* echo);
-/* HIP-event time (ms) of the four kernels of the last launch, after a sync: layer scalars, vertical distribution and echoes,
- * f0 / f1 tables, map. */
+/* HIP-event time (ms) of the four stages of the last launch, after a sync: layer scalars, vertical distribution and echoes,
+ * tables (f0 / f1; with Halimi14 its three kernels summed), map. */
 int32_t smrt_sar_kernel_ms(smrt_dort_ctx* ctx, double* ms4);
 /* [sizeof(smrt_sar_params), offset of every field in declaration order] as compiled; returns the number of entries. */
 int32_t smrt_sar_abi(int32_t* out, int32_t capacity);

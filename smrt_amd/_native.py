@@ -482,8 +482,12 @@ class SarParams(C.Structure):
         "roll_angle", "sigma_p", "theta_lim", "gamma_x", "gamma_y", "l_gamma", "lz", "pu", "nu_coherent")] + [(name, C.c_int32) for name in (
             "ngate", "ndoppler", "oversampling_time", "oversampling_doppler", "return_oversampled", "n_rows", "n_tables", "reserved")] + [
         ("table_sigma", C.POINTER(C.c_double)), ("table_index", C.POINTER(C.c_int32)), ("boundary_values", C.POINTER(C.c_double)),
-        ("row_map", C.POINTER(C.c_int32))]
+        ("row_map", C.POINTER(C.c_int32))] + [(name, C.c_int32) for name in (
+            "delay_doppler_model", "slant_range_correction", "delay_window_widening", "reserved2")] + [(name, C.c_double) for name in (
+                "h14_pu", "h14_gamma", "burst_duration")]
 
+
+SAR_MODELS = {"dinardo18": 0, "halimi14": 1}   # include/smrt_dort.h: SMRT_SAR_DINARDO18, SMRT_SAR_HALIMI14
 
 # (sigma_g, A_g) of the Gaussian that stands for the point target response, by "<approximation>:<Doppler window>"
 # (smrt/rtsolver/delay_doppler_model/delay_doppler_utils.py: MacArthur 1976, 1978; Brown 1977; Ray et al. 2015; Dinardo et al. 2018;
@@ -510,14 +514,24 @@ class PackedSarParams:
     (table_sigma) with the index of every snowpack into them, boundary_values [S][Lmax + 1][4] and row_map [S][2 (Lmax + 1) + 2]."""
 
     def __init__(self, sensor, table_sigma, table_index, boundary_values, row_map, n_rows=1, oversampling_time=4, oversampling_doppler=4,
-                 return_oversampled=False, ptr_doppler="gaussian-smrt"):
+                 return_oversampled=False, ptr_doppler="gaussian-smrt", model="dinardo18", slant_range_correction=True,
+                 delay_window_widening=1):
         from .core.globalconstants import C_SPEED
 
         s = SarParams()
         f, h, B = float(sensor.frequency), float(sensor.altitude), float(sensor.pulse_bandwidth)
         prf, velocity, alpha, ndoppler = float(sensor.pulse_repetition_frequency), float(sensor.velocity), float(sensor.alpha), int(sensor.ndoppler)
         wavelength = C_SPEED / f
-        sigma_g, a_g = ptr_gaussian_approximation(ptr_doppler, sensor.doppler_window)
+        s.delay_doppler_model = SAR_MODELS[model]
+        if model == "halimi14":   # (H14 after eq. 3 and eq. 14, 19; the constants of Dinardo18 below are filled and not read)
+            beamwidth = (float(sensor.beamwidth_alongtrack) + float(sensor.beamwidth_acrosstrack)) / 2
+            s.slant_range_correction, s.delay_window_widening = int(bool(slant_range_correction)), int(delay_window_widening)
+            s.h14_pu = wavelength ** 2 * float(sensor.antenna_gain) ** 2 * C_SPEED / (4 * (4 * np.pi) ** 2 * h ** 3) * ndoppler ** 2
+            s.h14_gamma = 1 / (2 * np.log(2)) * np.sin(np.deg2rad(beamwidth)) ** 2
+            s.burst_duration = ndoppler / prf
+            sigma_g, a_g = 1.0, 1.0
+        else:
+            sigma_g, a_g = ptr_gaussian_approximation(ptr_doppler, sensor.doppler_window)
         lx = (C_SPEED * h * prf) / (2 * velocity * ndoppler * f)            # R15 eq. 14, along track
         ly = np.sqrt(C_SPEED * h / (alpha * B))                              # R15 eq. 21, across track
         lz = C_SPEED / (2 * B)

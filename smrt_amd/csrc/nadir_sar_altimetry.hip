@@ -1,7 +1,8 @@
 // The nadir SAR altimetry solver of libsmrt_dort.so (include/smrt_dort.h: smrt_sar_*): its four kernels -- one lane per
 // (pair, layer) for the layer scalars, one workgroup per pair for the vertical distribution and the echo of the boundaries, one
 // lane per sample of the f0 / f1 tables, one workgroup per (pair, coarse Doppler bin) for the map; arithmetic in
-// nadir_sar_altimetry_kernel.hpp -- and the host side: buffers on the DORT context, upload / launch / sync / download and the
+// nadir_sar_altimetry_kernel.hpp; with the model of Halimi et al. 2014 the table stage is three kernels (one workgroup per
+// delay, per table, per table and Doppler column) and the map kernel its other instantiation -- and the host side: buffers on the DORT context, upload / launch / sync / download and the
 // one-shot call.
 #include <hip/hip_runtime.h>
 #include <cmath>
@@ -36,17 +37,34 @@ __global__ void __launch_bounds__(kSarThreads) sar_tables_kernel(SarBatch b) {
     sar_table_item(b, idx);
 }
 
+// The table stage of Halimi14: one workgroup per delay of the widened window, per table, per (table, Doppler column).
+__global__ void __launch_bounds__(kSarThreads) sar_h14_doppler_kernel(SarBatch b) {
+    extern __shared__ double sar_h14_doppler_lds[];
+    sar_h14_doppler_row(b, (int)blockIdx.x, threadIdx.x, kSarThreads, (unsigned char*)sar_h14_doppler_lds);
+}
+
+__global__ void __launch_bounds__(kSarThreads) sar_h14_kernel_kernel(SarBatch b) {
+    extern __shared__ double sar_h14_kernel_lds[];
+    sar_h14_kernel_table(b, (int)blockIdx.x, threadIdx.x, kSarThreads, (unsigned char*)sar_h14_kernel_lds);
+}
+
+__global__ void __launch_bounds__(kSarThreads) sar_h14_delay_kernel(SarBatch b) {
+    extern __shared__ double sar_h14_delay_lds[];
+    sar_h14_delay_column(b, (int)(blockIdx.x / b.ND), (int)(blockIdx.x % b.ND), threadIdx.x, kSarThreads, (unsigned char*)sar_h14_delay_lds);
+}
+
+template <int MODEL>
 __global__ void __launch_bounds__(kSarThreads) sar_combine_kernel(SarBatch b) {
     extern __shared__ double sar_combine_lds[];
-    sar_combine_item(b, blockIdx.x / b.ndoppler, (int)(blockIdx.x % b.ndoppler), threadIdx.x, kSarThreads, (unsigned char*)sar_combine_lds);
+    sar_combine_model<MODEL>(b, blockIdx.x / b.ndoppler, (int)(blockIdx.x % b.ndoppler), threadIdx.x, kSarThreads, (unsigned char*)sar_combine_lds);
 }
 
 struct SarState : solver_host::InputState {
     DevBuf &hostlayer = buf(), &hostcoeff = buf(), &tabsigma = buf(), &tabindex = buf(), &bv = buf(), &rowmap = buf();
     DevBuf &stage = buf(), &bs = buf(), &prefix = buf(), &vsd = buf(), &zgate = buf(), &status = buf(), &layer = buf();
-    DevBuf &tables = buf(), &echo = buf(), &out = buf();
+    DevBuf &tables = buf(), &echo = buf(), &out = buf(), &h14doppler = buf(), &h14kernel = buf();
     SarBatch dev{};
-    size_t lds_vertical = 0, lds_combine = 0;
+    size_t lds_vertical = 0, lds_combine = 0, lds_h14_doppler = 0, lds_h14_kernel = 0, lds_h14_delay = 0;
     bool uploaded = false;
     bool timed = false;   // events 0 .. 4 around the four kernels of the last launch
 };
@@ -71,7 +89,8 @@ int32_t smrt_sar_abi(int32_t* out, int32_t capacity) {
                             SMRT_OFF(gamma_y), SMRT_OFF(l_gamma), SMRT_OFF(lz), SMRT_OFF(pu), SMRT_OFF(nu_coherent), SMRT_OFF(ngate),
                             SMRT_OFF(ndoppler), SMRT_OFF(oversampling_time), SMRT_OFF(oversampling_doppler), SMRT_OFF(return_oversampled),
                             SMRT_OFF(n_rows), SMRT_OFF(n_tables), SMRT_OFF(reserved), SMRT_OFF(table_sigma), SMRT_OFF(table_index),
-                            SMRT_OFF(boundary_values), SMRT_OFF(row_map)};
+                            SMRT_OFF(boundary_values), SMRT_OFF(row_map), SMRT_OFF(delay_doppler_model), SMRT_OFF(slant_range_correction),
+                            SMRT_OFF(delay_window_widening), SMRT_OFF(reserved2), SMRT_OFF(h14_pu), SMRT_OFF(h14_gamma), SMRT_OFF(burst_duration)};
 #undef SMRT_OFF
     return solver_host::copy_table(desc, out, capacity);
 }
@@ -109,6 +128,8 @@ int32_t smrt_sar_upload_pairs(smrt_dort_ctx* ctx, const smrt_batch* b, const smr
     d.prf = p->pulse_repetition_frequency; d.wavelength = p->wavelength; d.velocity = p->velocity; d.alpha = p->alpha;
     d.pitch = p->pitch_angle; d.roll = p->roll_angle; d.sigma_p = p->sigma_p; d.theta_lim = p->theta_lim;
     d.gamma_x = p->gamma_x; d.gamma_y = p->gamma_y; d.l_gamma = p->l_gamma; d.lz = p->lz; d.pu = p->pu; d.nu_coherent = p->nu_coherent;
+    const bool h14 = p->delay_doppler_model == SMRT_SAR_HALIMI14;
+    if (h14) sar_h14_setup(d, p->slant_range_correction ? 1 : 0, p->delay_window_widening, p->h14_pu, p->h14_gamma, p->burst_duration);
     using solver_host::upload;
     if (solver_host::upload_batch(ctx, st, b, pairs, fo)) return -1;   // (fo.sub_kind is none: the substrate is not read)
     if (b->host_layer && upload(ctx, st->hostlayer, b->host_layer, SL * 4 * sizeof(double), fo.host_layer)) return -1;
@@ -124,7 +145,12 @@ int32_t smrt_sar_upload_pairs(smrt_dort_ctx* ctx, const smrt_batch* b, const smr
     HIPCHK(st->zgate.reserve(NP * lb.n_out * sizeof(double)));
     HIPCHK(st->status.reserve(NP * sizeof(int32_t)));
     HIPCHK(st->layer.reserve(NP * L * 5 * sizeof(double)));
-    HIPCHK(st->tables.reserve((size_t)p->n_tables * 2 * lb.N * d.ND * sizeof(double)));
+    HIPCHK(st->tables.reserve((size_t)p->n_tables * (h14 ? 1 : 2) * lb.N * d.ND * sizeof(double)));
+    if (h14) {
+        HIPCHK(st->h14doppler.reserve((size_t)d.ND * d.N_wide * sizeof(double)));
+        HIPCHK(st->h14kernel.reserve((size_t)p->n_tables * d.M * sizeof(double)));
+        d.h14_doppler = (double*)st->h14doppler.p; d.h14_kernel = (double*)st->h14kernel.p;
+    }
     HIPCHK(st->echo.reserve(NP * (L + 1) * SAR_ECHO * sizeof(double)));
     HIPCHK(st->out.reserve(NP * stride * sizeof(double)));
     fo.stage = (double*)st->stage.p; fo.layer_out = (double*)st->layer.p;
@@ -132,7 +158,10 @@ int32_t smrt_sar_upload_pairs(smrt_dort_ctx* ctx, const smrt_batch* b, const smr
     lb.z_gate = (double*)st->zgate.p; lb.status = (int*)st->status.p;
     d.tables = (double*)st->tables.p; d.echo = (double*)st->echo.p; d.out = (double*)st->out.p;
     st->lds_vertical = lrm_vertical_lds_bytes(lb.N, (int)L);
-    st->lds_combine = sar_combine_lds_bytes(lb.N, d.osd);
+    st->lds_combine = h14 ? sar_h14_combine_lds_bytes(lb.N, d.osd) : sar_combine_lds_bytes(lb.N, d.osd);
+    st->lds_h14_doppler = sar_h14_doppler_lds_bytes(d.ND);
+    st->lds_h14_kernel = h14 ? sar_h14_kernel_lds_bytes(d.M) : 0;
+    st->lds_h14_delay = h14 ? sar_h14_delay_lds_bytes(d.N_wide, d.M) : 0;
     if (solver_host::uploads_done(ctx)) return -1;
     st->dev = d;
     st->uploaded = true;
@@ -149,7 +178,14 @@ int32_t smrt_sar_launch(smrt_dort_ctx* ctx) {
     const long long items = d.lrm.fo.n_pairs * d.lrm.fo.Lmax, samples = (long long)d.n_tab * d.lrm.N * d.ND;
     // (a per-function setting shared by every context of the process: set for THIS batch at every launch)
     HIPCHK(hipFuncSetAttribute((const void*)sar_vertical_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)st->lds_vertical));
-    HIPCHK(hipFuncSetAttribute((const void*)sar_combine_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)st->lds_combine));
+    const bool h14 = d.model == kSarHalimi14;
+    const void* combine = h14 ? (const void*)sar_combine_kernel<kSarHalimi14> : (const void*)sar_combine_kernel<kSarDinardo18>;
+    HIPCHK(hipFuncSetAttribute(combine, hipFuncAttributeMaxDynamicSharedMemorySize, (int)st->lds_combine));
+    if (h14) {
+        HIPCHK(hipFuncSetAttribute((const void*)sar_h14_doppler_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)st->lds_h14_doppler));
+        HIPCHK(hipFuncSetAttribute((const void*)sar_h14_kernel_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)st->lds_h14_kernel));
+        HIPCHK(hipFuncSetAttribute((const void*)sar_h14_delay_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)st->lds_h14_delay));
+    }
     st->rewind();
     if (solver_host::record(ctx, st)) return -1;
     hipLaunchKernelGGL(sar_layers_kernel, dim3((unsigned)((items + kSarThreads - 1) / kSarThreads)), dim3(kSarThreads), 0, ctx->stream, d);
@@ -158,10 +194,21 @@ int32_t smrt_sar_launch(smrt_dort_ctx* ctx) {
     hipLaunchKernelGGL(sar_vertical_kernel, dim3((unsigned)d.lrm.fo.n_pairs), dim3(kSarThreads), st->lds_vertical, ctx->stream, d);
     HIPCHK(hipGetLastError());
     if (solver_host::record(ctx, st)) return -1;
-    hipLaunchKernelGGL(sar_tables_kernel, dim3((unsigned)((samples + kSarThreads - 1) / kSarThreads)), dim3(kSarThreads), 0, ctx->stream, d);
+    if (h14) {   // (the three kernels of the table stage between one pair of events: smrt_sar_kernel_ms sums them)
+        hipLaunchKernelGGL(sar_h14_doppler_kernel, dim3((unsigned)d.N_wide), dim3(kSarThreads), st->lds_h14_doppler, ctx->stream, d);
+        HIPCHK(hipGetLastError());
+        hipLaunchKernelGGL(sar_h14_kernel_kernel, dim3((unsigned)d.n_tab), dim3(kSarThreads), st->lds_h14_kernel, ctx->stream, d);
+        HIPCHK(hipGetLastError());
+        hipLaunchKernelGGL(sar_h14_delay_kernel, dim3((unsigned)((long long)d.n_tab * d.ND)), dim3(kSarThreads), st->lds_h14_delay, ctx->stream, d);
+    } else {
+        hipLaunchKernelGGL(sar_tables_kernel, dim3((unsigned)((samples + kSarThreads - 1) / kSarThreads)), dim3(kSarThreads), 0, ctx->stream, d);
+    }
     HIPCHK(hipGetLastError());
     if (solver_host::record(ctx, st)) return -1;
-    hipLaunchKernelGGL(sar_combine_kernel, dim3((unsigned)(d.lrm.fo.n_pairs * d.ndoppler)), dim3(kSarThreads), st->lds_combine, ctx->stream, d);
+    if (h14)
+        hipLaunchKernelGGL(sar_combine_kernel<kSarHalimi14>, dim3((unsigned)(d.lrm.fo.n_pairs * d.ndoppler)), dim3(kSarThreads), st->lds_combine, ctx->stream, d);
+    else
+        hipLaunchKernelGGL(sar_combine_kernel<kSarDinardo18>, dim3((unsigned)(d.lrm.fo.n_pairs * d.ndoppler)), dim3(kSarThreads), st->lds_combine, ctx->stream, d);
     HIPCHK(hipGetLastError());
     if (solver_host::record(ctx, st)) return -1;
     st->timed = true;

@@ -10,6 +10,8 @@
 //   sar_combine_item    one workgroup per (pair, coarse Doppler bin): the fine columns of the base map (D18 eq. 22, nu = 0) in
 //                       LDS, the direct convolution with the volume backscatter, the shifted and scaled columns of the
 //                       boundaries at their own nu, the row map, the mean over the oversampling blocks.
+// With the model of Halimi et al. 2014 (delay_doppler_model/halimi14.py) the table stage is sar_h14_doppler_row,
+// sar_h14_kernel_table and sar_h14_delay_column instead, and sar_combine_model<kSarHalimi14> reads the one table of the pair.
 //
 // With -DSMRT_HOST_EMU (g++, the CPU tests) a workgroup is one thread.
 #pragma once
@@ -35,7 +37,14 @@ struct SarBatch {
     double* tables;                  // [n_tab][2][N][ND]
     double* echo;                    // [n_pairs][Lmax + 1][SAR_ECHO]
     double* out;                     // [n_pairs][out_rows][n_t][n_d]
+    // Halimi et al. 2014 (model == kSarHalimi14; all zero with Dinardo18): `tables` is then [n_tab][ND][N], ONE table per
+    // sigma_surface, delay fastest
+    int model, slant, N_wide, M;     // N_wide = N x delay_window_widening; M = 2 (N / 2) - 1 samples of the delay kernel
+    double h14_pu, h14_gamma, idelta_r1;
+    double* h14_doppler;             // [ND][N_wide] the impulse response convolved along Doppler, delay fastest
+    double* h14_kernel;              // [n_tab][M] sinc^2 convolved with the height distribution
 };
+enum { kSarDinardo18 = 0, kSarHalimi14 = 1 };
 
 // ---- I_v(x) e^-x for v = -3/4, -1/4, 1/4, 3/4 and x >= 0 ---------------------------------------------------------------------
 // which: 0 .. 3 in that order.  The ascending series has positive terms only; the asymptotic expansion depends on v^2.
@@ -137,11 +146,133 @@ SMRT_DEV void sar_table_item(const SarBatch& b, long long idx) {
     tab[(size_t)N * ND + (size_t)n * ND + c] = sar_f1(xi);
 }
 
+// ---- the table of Halimi et al. 2014 (delay_doppler_model/halimi14.py, delay_doppler_utils.py) ---------------------------------
+// The flat-surface impulse response (H14 eq. 11-14) is closed form; the point target responses and the height distribution
+// enter through three linear convolutions ("same" alignment of scipy.signal.fftconvolve), made here by direct summation:
+// a thread owns consecutive outputs, so the sliding operand is read conflict-free and the other one as a broadcast.
+inline size_t sar_h14_doppler_lds_bytes(int ND) { return (size_t)3 * ND * sizeof(double); }            // phi, impulse response, sinc^2
+inline size_t sar_h14_kernel_lds_bytes(int M) { return (size_t)2 * M * sizeof(double); }                // sinc^2, Gaussian
+inline size_t sar_h14_delay_lds_bytes(int N_wide, int M) { return ((size_t)N_wide + M) * sizeof(double); }   // column, delay kernel
+inline size_t sar_h14_combine_lds_bytes(int N, int osd) { return (size_t)N * (1 + 3 * (size_t)osd) * sizeof(double); }
+
+// What the host derives of smrt_sar_params for Halimi14, once the sensor and the shape are in `d` (the device launch and the CPU
+// build alike): the shapes, and idelta_r1 of delay_doppler_utils.py:_compute_idelta_r1 (H14 eq. 19 in samples, with the Earth's curvature).
+inline void sar_h14_setup(SarBatch& d, int slant, int widening, double h14_pu, double h14_gamma, double burst_duration) {
+    d.model = kSarHalimi14; d.slant = slant; d.N_wide = d.lrm.N * widening; d.M = 2 * (d.lrm.N / 2) - 1;
+    d.h14_pu = h14_pu; d.h14_gamma = h14_gamma;
+    const double f1 = 1.0 / burst_duration / d.osd;
+    const double delta_r1 = f1 * f1 * (d.alpha * d.lrm.altitude * (d.wavelength * d.wavelength) / (8.0 * (d.velocity * d.velocity)));
+    d.idelta_r1 = delta_r1 * (2.0 / kCSpeed * d.lrm.bandwidth * d.lrm.os);
+}
+
+SMRT_DEV double sar_sinc2(double x) {   // numpy.sinc(x)^2
+    if (x == 0.0) return 1.0;
+    const double s = sin(kPi * x) / (kPi * x);
+    return s * s;
+}
+
+SMRT_DEV double sar_doppler_frequency(const SarBatch& b, int c) {
+    return (-(double)(b.ndoppler / 2 * b.osd) + 0.5 + c) * (b.prf / ((double)b.osd * b.ndoppler));
+}
+
+// One workgroup per delay n of the widened window: phi (eq. 12; NaN outside the circle), its difference along Doppler as
+// halimi14.py:diff_cyclic takes it -- the LAST column is phi[0] - phi[1], not a cyclic difference, and negative --, NaN -> 0, the
+// convolution with the Doppler point target response (eq. 15) times delta_fn.  Stored delay fastest.
+SMRT_DEV void sar_h14_doppler_row(const SarBatch& b, int n, int tid, int nt, unsigned char* lds) {
+    const int ND = b.ND;
+    double* phi = (double*)lds;
+    double* F = phi + ND;
+    double* g = F + ND;
+    const double tau = sar_tau(b, n), h = b.lrm.altitude;
+    const double rho2 = h * tau / b.alpha * kCSpeed;
+    for (int c = tid; c < ND; c += nt) {
+        const double fn = sar_doppler_frequency(b, c);
+        const double yn = h * b.wavelength / (2.0 * b.velocity) * fn;
+        const double xn = rho2 - yn * yn;
+        phi[c] = xn > 0.0 ? atan(yn / sqrt(xn)) : NAN;
+        g[c] = sar_sinc2(fn / (b.prf / b.ndoppler));
+    }
+    lrm_sync();
+    const double pref = b.h14_pu / kPi * exp(-4.0 * kCSpeed * tau / (b.alpha * b.h14_gamma * h));
+    for (int c = tid; c < ND; c += nt) {
+        const double d = c < ND - 1 ? phi[c + 1] - phi[c] : phi[0] - phi[1];
+        const double f = pref * d;
+        F[c] = f != f ? 0.0 : f;
+    }
+    lrm_sync();
+    const int s = (ND - 1) / 2;
+    const double delta_fn = b.prf / ND;
+    for (int c = tid; c < ND; c += nt) {
+        const int lo = c + s - (ND - 1) > 0 ? c + s - (ND - 1) : 0, hi = c + s < ND - 1 ? c + s : ND - 1;
+        double acc = 0.0;
+        for (int k = lo; k <= hi; ++k) acc += F[k] * g[c + s - k];
+        b.h14_doppler[(size_t)c * b.N_wide + n] = acc * delta_fn;
+    }
+}
+
+// One workgroup per table: the time point target response (eq. 6) on the reference's 2 (N / 2) - 1 samples, convolved with the
+// Gaussian height distribution (eq. 5) sampled on the same points when sigma_surface > 0 -- also where it is narrower than the
+// sample spacing and the samples no longer sum to one --, left alone when it is 0.
+SMRT_DEV void sar_h14_kernel_table(const SarBatch& b, int t, int tid, int nt, unsigned char* lds) {
+    const int M = b.M, half = b.lrm.N / 2;
+    double* p = (double*)lds;
+    double* q = p + M;
+    const double dtau = 1.0 / (b.lrm.os * b.lrm.bandwidth), ss = 2.0 * b.tab_sigma[t] / kCSpeed;
+    const bool rough = b.tab_sigma[t] > 0.0;
+    for (int j = tid; j < M; j += nt) {
+        const double ct = (double)(j - half + 1) * dtau;
+        p[j] = sar_sinc2(ct / (1.0 / b.lrm.bandwidth));
+        q[j] = rough ? exp(-(ct * ct) / (2.0 * ss * ss)) / (sqrt(2.0 * kPi) * ss) : 0.0;
+    }
+    lrm_sync();
+    for (int m = tid; m < M; m += nt) {
+        double acc = p[m];
+        if (rough) {
+            const int c = m + half - 1;   // p[j] q[c - j]
+            const int lo = c - (M - 1) > 0 ? c - (M - 1) : 0, hi = c < M - 1 ? c : M - 1;
+            acc = 0.0;
+            for (int j = lo; j <= hi; ++j) acc += p[j] * q[c - j];
+            acc *= dtau;
+        }
+        b.h14_kernel[(size_t)t * M + m] = acc;
+    }
+}
+
+// One workgroup per (table, Doppler column): the convolution along the delay (eq. 7) times dtau, times Nb / prf, and the delay
+// compensation (eq. 19): the column moves floor(idelta_r1 (c - Nb / 2 + 0.5)^2) rows up, zeros come in below, and a column whose
+// shift reaches N_wide is all zero.  Only the first N rows are kept.
+SMRT_DEV void sar_h14_delay_column(const SarBatch& b, int t, int c, int tid, int nt, unsigned char* lds) {
+    const int N = b.lrm.N, NW = b.N_wide, M = b.M, half = N / 2;
+    double* a = (double*)lds;
+    double* k = a + NW;
+    for (int j = tid; j < NW; j += nt) a[j] = b.h14_doppler[(size_t)c * NW + j];
+    for (int m = tid; m < M; m += nt) k[m] = b.h14_kernel[(size_t)t * M + m];
+    lrm_sync();
+    const double off = (double)(c - b.ND / 2) + 0.5;
+    const double up = b.slant ? floor(b.idelta_r1 * (off * off)) : 0.0;
+    const int shift = up < (double)NW ? (int)up : NW;
+    const double scale = 1.0 / (b.lrm.os * b.lrm.bandwidth) * ((double)b.ND / b.prf);
+    double* tab = b.tables + ((size_t)t * b.ND + c) * N;
+    for (int n = tid; n < N; n += nt) {
+        const int r = n + shift;
+        double acc = 0.0;
+        if (r < NW) {
+            const int e = r + half - 1;   // a[j] k[e - j]
+            const int lo = e - (M - 1) > 0 ? e - (M - 1) : 0, hi = e < NW - 1 ? e : NW - 1;
+            for (int j = lo; j <= hi; ++j) acc += a[j] * k[e - j];
+        }
+        tab[n] = acc * scale;
+    }
+}
+
 // ---- the map ----------------------------------------------------------------------------------------------------------------
-// LDS of the kernel: v [N]; D, P1, V, W [osd][N] doubles
+// LDS of the kernel: v [N]; D, P1, V, W [osd][N] doubles (Halimi14: no P1)
 inline size_t sar_combine_lds_bytes(int N, int osd) { return (size_t)N * (1 + 4 * (size_t)osd) * sizeof(double); }
 
-SMRT_DEV void sar_combine_item(const SarBatch& b, long long i, int bin, int tid, int nt, unsigned char* lds) {
+// MODEL is where the fine columns of a pair come from and how a boundary weighs them: kSarDinardo18, D and P1 of D18 eq. 22 from
+// the f0 / f1 tables, a boundary at its own nu; kSarHalimi14, the pair's table as it is, the same for every boundary.
+template <int MODEL>
+SMRT_DEV void sar_combine_model(const SarBatch& b, long long i, int bin, int tid, int nt, unsigned char* lds) {
     const LrmBatch& lb = b.lrm;
     const long long gp = lrm_global_pair(lb, i);
     const int s = (int)(gp % lb.fo.S);
@@ -150,7 +281,7 @@ SMRT_DEV void sar_combine_item(const SarBatch& b, long long i, int bin, int tid,
     double* v = (double*)lds;
     double* D = v + N;
     double* P1 = D + (size_t)osd * N;
-    double* V = P1 + (size_t)osd * N;   // the convolution with the volume backscatter, made once for its row and for the total
+    double* V = P1 + (MODEL == kSarDinardo18 ? (size_t)osd * N : 0);   // the convolution with the volume backscatter, made once for its row and for the total
     double* W = V + (size_t)osd * N;
     double* out = b.out + (size_t)i * b.out_rows * b.n_t * b.n_d;
     if (lb.status[i] != ST_OK) {
@@ -161,19 +292,24 @@ SMRT_DEV void sar_combine_item(const SarBatch& b, long long i, int bin, int tid,
         }
         return;
     }
-    const double ss = b.tab_sigma[b.tab_index[s]];
-    const double* tab = b.tables + (size_t)b.tab_index[s] * 2 * N * ND;
-    // (dinardo18.py computes the tanh term of D18 eq. 26 and discards it: a constant correction for roll > 0, none otherwise)
-    const double tk0 = 1.0 - (b.roll > 0.0 ? b.roll * (2.0 * b.gamma_y * b.roll) : 0.0);
-    for (int idx = tid; idx < osd * N; idx += nt) {
-        const int cc = idx / N, n = idx % N, c = bin * osd + cc;
-        const double look = sar_look_angle(b, c), sigma_c = sar_sigma_c(b, look, ss), f = sar_f(b, n);
-        const double gl = 1.0 / lb.bandwidth / sigma_c, dp = look - b.pitch;
-        const double gamma_kl = exp(-b.gamma_y * b.roll * b.roll - b.gamma_x * (dp * dp) - b.gamma_y * f) * cosh(2.0 * b.gamma_y * b.roll * sqrt(f));
-        const double pref = b.pu * gamma_kl / sqrt(sigma_c);
-        const double p1 = pref * (ss / b.l_gamma * gl * (ss / b.lz)) * tab[(size_t)N * ND + (size_t)n * ND + c];
-        P1[idx] = p1;
-        D[idx] = pref * tab[(size_t)n * ND + c] + tk0 * p1;
+    if constexpr (MODEL == kSarHalimi14) {
+        const double* tab = b.tables + ((size_t)b.tab_index[s] * ND + (size_t)bin * osd) * N;   // the osd columns are contiguous
+        for (int idx = tid; idx < osd * N; idx += nt) D[idx] = tab[idx];
+    } else {
+        const double ss = b.tab_sigma[b.tab_index[s]];
+        const double* tab = b.tables + (size_t)b.tab_index[s] * 2 * N * ND;
+        // (dinardo18.py computes the tanh term of D18 eq. 26 and discards it: a constant correction for roll > 0, none otherwise)
+        const double tk0 = 1.0 - (b.roll > 0.0 ? b.roll * (2.0 * b.gamma_y * b.roll) : 0.0);
+        for (int idx = tid; idx < osd * N; idx += nt) {
+            const int cc = idx / N, n = idx % N, c = bin * osd + cc;
+            const double look = sar_look_angle(b, c), sigma_c = sar_sigma_c(b, look, ss), f = sar_f(b, n);
+            const double gl = 1.0 / lb.bandwidth / sigma_c, dp = look - b.pitch;
+            const double gamma_kl = exp(-b.gamma_y * b.roll * b.roll - b.gamma_x * (dp * dp) - b.gamma_y * f) * cosh(2.0 * b.gamma_y * b.roll * sqrt(f));
+            const double pref = b.pu * gamma_kl / sqrt(sigma_c);
+            const double p1 = pref * (ss / b.l_gamma * gl * (ss / b.lz)) * tab[(size_t)N * ND + (size_t)n * ND + c];
+            P1[idx] = p1;
+            D[idx] = pref * tab[(size_t)n * ND + c] + tk0 * p1;
+        }
     }
     for (int n = tid; n < N; n += nt) v[n] = lb.vsd[(size_t)i * N + n];
     lrm_sync();
@@ -202,8 +338,12 @@ SMRT_DEV void sar_combine_item(const SarBatch& b, long long i, int bin, int tid,
                     const double echo = e[k * SAR_ECHO + (coherent ? SAR_ECHO_COHERENT : SAR_ECHO_INCOHERENT)];
                     const int m = n - (int)e[k * SAR_ECHO + SAR_ECHO_SHIFT];
                     if (!(echo > 0.0) || m < 0) continue;
-                    const double nu = coherent ? b.nu_coherent : bv[k * SAR_BV + SAR_BV_NU];
-                    acc += echo * (exp(-nu * (look * look) - nu * sar_f(b, m)) * (d[m] + nu / b.gamma_y * p1[m]));
+                    if constexpr (MODEL == kSarHalimi14) {
+                        acc += echo * d[m];
+                    } else {
+                        const double nu = coherent ? b.nu_coherent : bv[k * SAR_BV + SAR_BV_NU];
+                        acc += echo * (exp(-nu * (look * look) - nu * sar_f(b, m)) * (d[m] + nu / b.gamma_y * p1[m]));
+                    }
                 }
             W[idx] = acc;
         }
@@ -221,6 +361,10 @@ SMRT_DEV void sar_combine_item(const SarBatch& b, long long i, int bin, int tid,
         }
         lrm_sync();
     }
+}
+
+SMRT_DEV void sar_combine_item(const SarBatch& b, long long i, int bin, int tid, int nt, unsigned char* lds) {
+    sar_combine_model<kSarDinardo18>(b, i, bin, tid, nt, lds);
 }
 
 }  // namespace smrt

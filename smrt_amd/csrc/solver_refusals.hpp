@@ -162,6 +162,17 @@ inline const char* nadir_sar_altimetry(const smrt_batch* b, const smrt_sar_param
         return "invalid sensor parameters";
     if (!p->table_sigma || !p->table_index || !p->boundary_values || !p->row_map || p->n_tables < 1) return "the tables, the boundary values or the row map are missing";
     if (p->n_rows < 1) return "n_rows must be positive";
+    if (p->delay_doppler_model != SMRT_SAR_DINARDO18 && p->delay_doppler_model != SMRT_SAR_HALIMI14)
+        return "unknown delay_doppler_model: the nadir SAR altimetry solver has Dinardo18 (0) and Halimi14 (1)";
+    if (p->delay_doppler_model == SMRT_SAR_HALIMI14) {
+        if (p->delay_window_widening < 1) return "delay_window_widening must be at least 1";
+        if (p->ngate * p->oversampling_time < 2) return "Halimi14 needs at least two delay samples (its time point target response has 2 (N / 2) - 1)";
+        if (!(p->h14_pu > 0.0) || !(p->h14_gamma > 0.0) || !(p->burst_duration > 0.0)) return "invalid sensor parameters";
+        const long long n_wide = (long long)p->ngate * p->oversampling_time * p->delay_window_widening;
+        const int nd = p->ndoppler * p->oversampling_doppler, m = 2 * (p->ngate * p->oversampling_time / 2) - 1;
+        if (n_wide > (1 << 20) || smrt::sar_h14_doppler_lds_bytes(nd) > kLrmLdsLimit || smrt::sar_h14_delay_lds_bytes((int)n_wide, m) > kLrmLdsLimit)
+            return "the widened delay window or the Doppler axis of Halimi14 do not fit the local data share";
+    }
     for (int t = 0; t < p->n_tables; ++t)
         if (!(p->table_sigma[t] >= 0.0)) return "sigma_surface must be non-negative";
     const int sources = 2 * (b->n_layers_max + 1) + 2;

@@ -21,20 +21,26 @@ Model.run is one launch per group (same sensor, same options), unless the maps o
 sigma_surface exceed OUTPUT_BUDGET bytes: the pairs of the group are then launched in as many parts as needed, each with the
 tables of its own sigma_surface only.
 
-Refused: any delay_doppler_model but Dinardo18; theta_inc != 0; an atmosphere; an interface or substrate without
-roughness_rms; a positive incoherent echo without mean_square_slope; skip_convolutions; a terrain that is not "normal"; an odd
+delay_doppler_model="halimi14" (Halimi et al. 2014) takes ptr_time / ptr_doppler (None or "sinc^2"),
+slant_range_correction and delay_window_widening in delay_doppler_model_options: one table per distinct sigma_surface, made on the
+device by direct convolution, for the volume and every boundary alike; no mean_square_slope is needed, and the coherent echo is
+added after a warning, as in the reference.
+
+Refused: any delay_doppler_model but Dinardo18 and Halimi14; theta_inc != 0; an atmosphere; an interface or substrate
+without roughness_rms; with Dinardo18 a positive incoherent echo without mean_square_slope; skip_convolutions; a terrain that is not "normal"; an odd
 ndoppler; a boundary with a positive echo later than the window.  Of smrt_amd's own: a dem or a slope_angle in the terrain_info.
 """
 import numpy as np
 
 from .._native import STATUS_MESSAGES, PackedLrmParams, PackedSarParams, ptr_gaussian_approximation
-from ..core.error import SMRTError
+from ..core.error import SMRTError, smrt_warn
 from ..core.globalconstants import C_SPEED
 from ..core.result import LabeledArray
 from ..core.sensor import Altimeter
 from ..core.terrain import TerrainInfo
 from ..interface.fresnel import reflection_diagonal
 from .delay_doppler_model.dinardo18 import Dinardo18  # noqa: F401  (delay_doppler_model=Dinardo18)
+from .delay_doppler_model.halimi14 import Halimi14  # noqa: F401  (delay_doppler_model=Halimi14)
 from .dort import get_context
 from .iterative_first_order import IterativeFirstOrder
 from .nadir_lrm_altimetry import NadirLRMAltimetry, _Solution as _LrmSolution, _without_substrate
@@ -53,16 +59,33 @@ class NadirSARAltimetry(NadirLRMAltimetry):
         if error_handling not in ("exception", "nan"):
             raise SMRTError("error_handling must be 'exception' or 'nan'")
         name = delay_doppler_model if isinstance(delay_doppler_model, str) else getattr(delay_doppler_model, "__name__", None)
-        if delay_doppler_model is not None and (name is None or name.lower() != "dinardo18"):
-            raise SMRTError("the nadir_sar_altimetry solver offers the Dinardo18 delay Doppler model only (the others rest on "
-                            "adaptive quadrature, FFT grids or a DEM)")
+        model = "dinardo18" if delay_doppler_model is None else (name or "").lower()
+        if model not in ("dinardo18", "halimi14"):
+            raise SMRTError("the nadir_sar_altimetry solver offers the Dinardo18 and the Halimi14 delay Doppler models only (the "
+                            "others rest on adaptive quadrature, FFT grids or a DEM)")
+        self.delay_doppler_model = model
         options = dict(delay_doppler_model_options or {})
-        unknown = set(options) - {"ptr_time", "ptr_doppler", "oversampling_time", "oversampling_doppler"}
-        if unknown:
-            raise SMRTError(f"Dinardo18 has no option {sorted(unknown)}: it takes ptr_time and ptr_doppler")
-        if not (options.get("ptr_time") or "gaussian").startswith("gaussian"):
-            raise SMRTError("Dinardo18 takes a Gaussian ptr_time only")
-        self.ptr_doppler = options.get("ptr_doppler", "gaussian-smrt")
+        self.ptr_doppler, self.slant_range_correction, self.delay_window_widening = "gaussian-smrt", True, 1
+        if model == "halimi14":   # (the solver's own oversampling factors govern, as in the reference)
+            unknown = set(options) - {"ptr_time", "ptr_doppler", "slant_range_correction", "delay_window_widening", "oversampling_time",
+                                      "oversampling_doppler"}
+            if unknown:
+                raise SMRTError(f"Halimi14 has no option {sorted(unknown)}: it takes ptr_time, ptr_doppler, slant_range_correction and "
+                                "delay_window_widening")
+            for what in ("ptr_time", "ptr_doppler"):
+                if options.get(what) not in (None, "sinc^2"):
+                    raise SMRTError(f"Halimi14 takes {what}=None or 'sinc^2' only (as the reference, which raises NotImplementedError)")
+            widening = options.get("delay_window_widening", 1)
+            if isinstance(widening, bool) or not isinstance(widening, (int, np.integer)) or widening < 1:
+                raise SMRTError("delay_window_widening must be a positive integer")
+            self.slant_range_correction, self.delay_window_widening = bool(options.get("slant_range_correction", True)), int(widening)
+        else:
+            unknown = set(options) - {"ptr_time", "ptr_doppler", "oversampling_time", "oversampling_doppler"}
+            if unknown:
+                raise SMRTError(f"Dinardo18 has no option {sorted(unknown)}: it takes ptr_time and ptr_doppler")
+            if not (options.get("ptr_time") or "gaussian").startswith("gaussian"):
+                raise SMRTError("Dinardo18 takes a Gaussian ptr_time only")
+            self.ptr_doppler = options.get("ptr_doppler", "gaussian-smrt")
         for what, value in (("oversampling_time", oversampling_time), ("oversampling_doppler", oversampling_doppler)):
             if isinstance(value, bool) or int(value) != value or value < 1:
                 raise SMRTError(what + " must be a positive integer")
@@ -97,17 +120,19 @@ class NadirSARAltimetry(NadirLRMAltimetry):
                             "vector has another length than its map otherwise)")
         if not float(sensor.velocity) > 0 or not float(sensor.pulse_repetition_frequency) > 0:
             raise SMRTError("a SAR altimeter needs its velocity and its pulse_repetition_frequency")
-        ptr_gaussian_approximation(self.ptr_doppler, sensor.doppler_window)
+        if self.delay_doppler_model == "dinardo18":
+            ptr_gaussian_approximation(self.ptr_doppler, sensor.doppler_window)
 
     def _check_snowpack(self, sp, sensor=None):
         if sp.atmosphere is not None:
             raise SMRTError("the nadir_sar_altimetry solver can not handle atmosphere.")
         info = getattr(sp, "terrain_info", None)
         info = TerrainInfo() if info is None else info
+        model = "Halimi14" if self.delay_doppler_model == "halimi14" else "Dinardo18"
         if info.distribution != "normal":
-            raise SMRTError("Dinardo18 is only available for a normally-distributed surface")
+            raise SMRTError(model + " is only available for a normally-distributed surface")
         if getattr(info, "dem", None) is not None or float(getattr(info, "slope_angle", 0) or 0) != 0:
-            raise SMRTError("the nadir_sar_altimetry solver takes no dem and no slope_angle (Dinardo18 reads neither)")
+            raise SMRTError(f"the nadir_sar_altimetry solver takes no dem and no slope_angle ({model} reads neither)")
         sigma = float(info.sigma_surface)
         if not sigma >= 0:
             raise SMRTError("terrain_info.sigma_surface must be non-negative")
@@ -161,7 +186,8 @@ class NadirSARAltimetry(NadirLRMAltimetry):
             self._check_sensor(sensor)
             key = tuple(float(getattr(sensor, a)) for a in (
                 "frequency", "altitude", "pulse_bandwidth", "beamwidth_alongtrack", "beamwidth_acrosstrack", "antenna_gain", "ngate",
-                "ndoppler", "nominal_gate", "pitch_angle", "roll_angle", "velocity", "pulse_repetition_frequency")) + (sensor.doppler_window,)
+                "ndoppler", "nominal_gate", "pitch_angle", "roll_angle", "velocity", "pulse_repetition_frequency")) + (
+                    sensor.doppler_window, self.delay_doppler_model, self.slant_range_correction, self.delay_window_widening)
             s_code[k] = keys.setdefault(key, len(keys))
         on_host = np.array([not isinstance(emmodel_names, str) and any(not isinstance(e, str) for e in emmodel_names[k])
                             for k in range(len(packs))], np.int64)
@@ -202,9 +228,13 @@ class NadirSARAltimetry(NadirLRMAltimetry):
             fine = sensor0.ngate * self.oversampling_time * sensor0.ndoppler * self.oversampling_doppler
             per_pair = n_rows * (fine if self.return_oversampled else sensor0.ngate * sensor0.ndoppler) * 8
             n_sigma = len(np.unique(sigma))
-            step = max(1, (OUTPUT_BUDGET - min(n_sigma, len(pairs)) * 2 * fine * 8) // per_pair)
+            # (Dinardo18: f0 and f1 per sigma_surface.  Halimi14: one table per sigma_surface, and once per launch the impulse
+            # response convolved along Doppler on the widened window)
+            halimi = self.delay_doppler_model == "halimi14"
+            table, fixed = (fine * 8, fine * self.delay_window_widening * 8) if halimi else (2 * fine * 8, 0)
+            step = max(1, (OUTPUT_BUDGET - fixed - min(n_sigma, len(pairs)) * table) // per_pair)
             if step < len(pairs):   # (several parts: each with at most `step` tables of its own)
-                step = max(1, OUTPUT_BUDGET // (per_pair + 2 * fine * 8))
+                step = max(1, (OUTPUT_BUDGET - fixed) // (per_pair + table))
             outs = []
             for begin in range(0, len(pairs), step):
                 part = pairs[begin:begin + step]
@@ -214,7 +244,9 @@ class NadirSARAltimetry(NadirLRMAltimetry):
                 table_index[part] = index
                 params = PackedSarParams(sensor0, table_sigma, table_index, values, row_map, n_rows=n_rows,
                                          oversampling_time=self.oversampling_time, oversampling_doppler=self.oversampling_doppler,
-                                         return_oversampled=self.return_oversampled, ptr_doppler=self.ptr_doppler)
+                                         return_oversampled=self.return_oversampled, ptr_doppler=self.ptr_doppler,
+                                         model=self.delay_doppler_model, slant_range_correction=self.slant_range_correction,
+                                         delay_window_widening=self.delay_window_widening)
                 with ctx.lock:
                     outs.append(ctx.sar_run(batch, params, pairs=None if full else part))
                 self.launches += 1
@@ -248,6 +280,7 @@ class NadirSARAltimetry(NadirLRMAltimetry):
         beta12 = 1 / (wavenumber * sensor0.altitude * beta0) ** 2 + beta0 ** 2 / 4
         values = np.zeros((S, Lmax + 1, 4))
         values[..., 0] = 1.0
+        tabulated = self.delay_doppler_model == "halimi14"
 
         def echo(obj, e1, e2, mu, substrate):
             args = (f, e1) if substrate else (f, e1, e2)
@@ -257,6 +290,8 @@ class NadirSARAltimetry(NadirLRMAltimetry):
             below = complex(obj.permittivity(f)) if substrate else e2
             specular = float(np.asarray(reflection_diagonal(e1, below, mu, 2), float)[0, 0])
             coherent = specular * float(np.exp(-4 * (wavenumber * obj.roughness_rms) ** 2 - (1 - mu[0] ** 2) / beta12) / beta12 / (4 * np.pi))
+            if tabulated:   # one map for the volume and every boundary: no mean square slope enters
+                return coherent, incoherent, 0.0
             if incoherent > 0 and getattr(obj, "mean_square_slope", None) is None:
                 raise SMRTError("the delay_doppler_model Dinardo18 relies on geometrical optics interfaces only (or non scattering "
                                 "interfaces): an interface with an incoherent echo needs a mean_square_slope")
@@ -273,6 +308,8 @@ class NadirSARAltimetry(NadirLRMAltimetry):
             if sp.substrate is not None:
                 mu = np.sqrt(1 - (1 - mu_i) / e[L].real)
                 values[s, L, 1:] = echo(sp.substrate, e[L], None, mu, True)
+        if tabulated and np.any(values[..., 1] > 0):   # (the reference adds it all the same, after this warning)
+            smrt_warn("This delay Doppler model is not compatible with coherent backscatter")
         return values
 
 

@@ -6,8 +6,10 @@ because packing it evaluates the transmission of every geometrical-optics interf
 SciPy restatement on the host (no GPU), then -- unless --host-only -- the resident-input rate (median of the HIP-event times of the
 four kernels over `steps` launches after `warmup`), the rate with H2D + D2H, and Model.run.  Writes
 profiles/nadir_sar_altimetry_rate.txt; a step that was not run or did not finish is recorded as "not measured"; every line names
-the processor it was measured on.  No rate is a gate.
-    python tools/bench_nadir_sar_altimetry.py [--host-only] [--out=FILE] [steps] [warmup] [snowpacks]"""
+the processor it was measured on.  No rate is a gate.  --model=halimi14 measures the delay-Doppler model of Halimi et al. 2014
+instead (into profiles/nadir_sar_altimetry_halimi14_rate.txt); --sigmas=K gives the snowpacks K distinct sigma_surface (default 2),
+which is the number of tables the table stage makes.
+    python tools/bench_nadir_sar_altimetry.py [--model=dinardo18|halimi14] [--sigmas=K] [--host-only] [--out=FILE] [steps] [warmup] [snowpacks]"""
 import json
 import os
 import subprocess
@@ -20,7 +22,11 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 REFERENCE_MS = 900     # what --step reference gave where the reference is installed (one core, median of four solves, one run)
-OUT = os.path.join(ROOT, "profiles", "nadir_sar_altimetry_rate.txt")
+REFERENCE_MS_HALIMI14 = 300
+MODEL = next((a.split("=", 1)[1].lower() for a in sys.argv[1:] if a.startswith("--model=")), "dinardo18")
+SIGMAS = int(next((a.split("=", 1)[1] for a in sys.argv[1:] if a.startswith("--sigmas=")), 2))
+OUT = os.path.join(ROOT, "profiles", "nadir_sar_altimetry_rate.txt" if MODEL == "dinardo18" else f"nadir_sar_altimetry_{MODEL}_rate.txt")
+OPTIONS = {} if MODEL == "dinardo18" else dict(delay_doppler_model=MODEL)
 LAYERS = 30
 
 
@@ -34,7 +40,7 @@ def snowpacks(n, seed=0):
     for k in range(n):     # 0.02 to 0.2 m per layer: every interface inside the window of 128 gates
         sp = make_snowpack(list(rng.uniform(0.02, 0.2, LAYERS)), "exponential", density=list(rng.uniform(250.0, 450.0, LAYERS)),
                            temperature=list(rng.uniform(245.0, 265.0, LAYERS)), corr_length=list(rng.uniform(1e-4, 3e-4, LAYERS)), interface=rough)
-        sp.terrain_info = TerrainInfo(sigma_surface=0.1 + 0.1 * (k % 2))
+        sp.terrain_info = TerrainInfo(sigma_surface=0.1 + 0.1 * (k % SIGMAS) / max(1, SIGMAS - 1))
         sps.append(sp)
     return sps
 
@@ -54,7 +60,7 @@ def packed(n):
 
     ctx.sar_run = spy
     try:
-        make_model("iba", "nadir_sar_altimetry").run(sar_altimeter_list.cryosat2_sarm(), snowpacks(n))
+        make_model("iba", "nadir_sar_altimetry", rtsolver_options=OPTIONS).run(sar_altimeter_list.cryosat2_sarm(), snowpacks(n))
     finally:
         del ctx.sar_run
     return ctx, kept["batch"], kept["params"]
@@ -63,7 +69,10 @@ def packed(n):
 def step_host(n, steps, warmup):
     import types
 
-    from nadir_sar_altimetry_restatement import solve_case
+    if MODEL == "halimi14":
+        from nadir_sar_altimetry_halimi14_restatement import solve_case
+    else:
+        from nadir_sar_altimetry_restatement import solve_case
     from smrt_amd.core.terrain import TerrainInfo
     from smrt_amd.inputs import sar_altimeter_list
     from smrt_amd.inputs.make_medium import make_interface, make_snowpack, make_soil
@@ -73,7 +82,7 @@ def step_host(n, steps, warmup):
     rng = np.random.RandomState(0)
     case = dict(name="bench", sensor="cryosat2_sarm", thickness=list(rng.uniform(0.02, 0.2, LAYERS)), density=list(rng.uniform(250.0, 450.0, LAYERS)),
                 temperature=list(rng.uniform(245.0, 265.0, LAYERS)), corr_length=list(rng.uniform(1e-4, 3e-4, LAYERS)),
-                interface=[dict(roughness_rms=0.005, corr_length=0.10)] * LAYERS, sigma_surface=0.2)
+                interface=[dict(roughness_rms=0.005, corr_length=0.10)] * LAYERS, sigma_surface=0.2, options=dict(OPTIONS, delay_doppler_model_options={}))
     solve_case(case, api)
     t0 = time.perf_counter()
     for _ in range(3):
@@ -115,11 +124,23 @@ def step_reference(n, steps, warmup):
     sp.terrain_info = TerrainInfo(sigma_surface=0.2)
     sensor, times = sar_altimeter_list.cryosat2_sarm(), []
     with contextlib.redirect_stdout(io.StringIO()):   # (the reference prints from __init__ and from Dinardo18)
-        m = make_model("iba", "nadir_sar_altimetry", rtsolver_options=dict(return_oversampled=True))
+        if MODEL == "halimi14":   # (without numba its delay compensation needs an integer floor: tests/golden/make_nadir_sar_altimetry_halimi14_fixtures.py)
+            from smrt.rtsolver.delay_doppler_model import delay_doppler_utils
+
+            class IntegerFloor:
+                def __getattr__(self, name):
+                    return getattr(np, name)
+
+                @staticmethod
+                def floor(x):
+                    return int(np.floor(x))
+
+            delay_doppler_utils.np = IntegerFloor()
+        m = make_model("iba", "nadir_sar_altimetry", rtsolver_options=dict(OPTIONS, return_oversampled=True))
         for _ in range(4):
             t0 = time.perf_counter()
             emmodels = m.prepare_emmodels(sensor, sp)
-            solver = m.rtsolver(return_oversampled=True) if isinstance(m.rtsolver, type) else m.rtsolver
+            solver = m.rtsolver(**dict(OPTIONS, return_oversampled=True)) if isinstance(m.rtsolver, type) else m.rtsolver
             solver.solve(sp, emmodels, sensor)
             times.append(time.perf_counter() - t0)
     return dict(ms_per_solve=float(np.median(times)) * 1e3)
@@ -155,7 +176,7 @@ def step_model(n, steps, warmup):
     from smrt_amd import make_model
     from smrt_amd.inputs import sar_altimeter_list
 
-    m, sensor, sps = make_model("iba", "nadir_sar_altimetry"), sar_altimeter_list.cryosat2_sarm(), snowpacks(n)
+    m, sensor, sps = make_model("iba", "nadir_sar_altimetry", rtsolver_options=OPTIONS), sar_altimeter_list.cryosat2_sarm(), snowpacks(n)
     times = []
     for k in range(max(1, warmup) + max(2, steps // 3)):
         t0 = time.perf_counter()
@@ -210,15 +231,17 @@ def main():
         print(json.dumps(STEPS[name](n, steps, warmup)))
         return
     steps, warmup, n = (int(a) for a in (args + ["10", "2", "128"][len(args):])[:3])
-    yardstick = f"{REFERENCE_MS} ms; re-measure with `python tools/bench_nadir_sar_altimetry.py --step reference 0 0 1`"
+    yardstick = (f"{REFERENCE_MS if MODEL == 'dinardo18' else REFERENCE_MS_HALIMI14} ms; re-measure with "
+                 f"`python tools/bench_nadir_sar_altimetry.py --model={MODEL} --step reference 0 0 1`")
     lines = ["nadir SAR altimetry solver: rates (tools/bench_nadir_sar_altimetry.py)",
-             f"batch: {n} snowpacks x {LAYERS} layers, cryosat2_sarm(), default options (Dinardo18, oversampling 4 x 4, two sigma_surface)",
+             f"batch: {n} snowpacks x {LAYERS} layers, cryosat2_sarm(), default options ({MODEL}, oversampling 4 x 4, {SIGMAS} distinct sigma_surface)",
              f"yardstick: the reference per solve on one CPU core (same case, on the machine that has the reference installed): {yardstick}"]
     for name in ("host", "resident", "transfers", "model"):
         if name != "host" and "--host-only" in sys.argv:
             lines.append(f"{name}: not measured")
             continue
-        cmd = ["timeout", "-k", "10", "300", sys.executable, os.path.abspath(__file__), "--step", name, str(steps), str(warmup), str(n)]
+        cmd = ["timeout", "-k", "10", "300", sys.executable, os.path.abspath(__file__), f"--model={MODEL}", f"--sigmas={SIGMAS}", "--step", name,
+               str(steps), str(warmup), str(n)]
         proc = subprocess.run(cmd, cwd=ROOT, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True)
         if proc.returncode != 0:
             lines.append(f"{name}: not measured (the step ended with status {proc.returncode})")
