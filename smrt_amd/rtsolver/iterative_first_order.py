@@ -29,20 +29,21 @@ value, not once per layer and simulation.
 """
 import numpy as np
 
-from .._native import STATUS_MESSAGES, PackedFirstOrderExtras
+from .._native import PackedFirstOrderExtras
 from ..core.error import SMRTError, smrt_warn
 from ..core.foreign import result_factory
 from ..core.result import LabeledArray, make_result
 from ..core.snowpack import substrate_kind
 from ..interface.flat import Flat
 from .dort import DORT, get_context
+from .solver_base import LayeredSolution, SolverBase, check_error_handling
 
 CONTRIBUTIONS = ["total", "order0_backscatter", "order1_direct_backscatter", "order1_double_bounce",
                  "order1_reflected_backscatter"]
 POLA = ["V", "H"]
 
 
-class IterativeFirstOrder(object):
+class IterativeFirstOrder(SolverBase):
     """error_handling: "exception" (default) raises on an invalid simulation, "nan" returns NaN for it and goes on.
     return_contributions: False (default) returns the total backscatter, True adds a leading `contribution` dimension
     ("total" first, then the four mechanisms).  `devices` (list of GPU indices; the first is used) is smrt_amd's own knob."""
@@ -51,68 +52,9 @@ class IterativeFirstOrder(object):
     NAME = "iterative_first_order"   # in the messages; a solver built on this one (iterative_second_order) sets its own
 
     def __init__(self, error_handling="exception", return_contributions=False, devices=None):
-        if error_handling not in ("exception", "nan"):
-            raise SMRTError("error_handling must be 'exception' or 'nan'")
-        self.error_handling = error_handling
+        self.error_handling = check_error_handling(error_handling)
         self.return_contributions = bool(return_contributions)
         self.devices = devices
-        self.launches = 0   # kernel launches (pairs of kernels) of the last solve: tests assert "one launch"
-
-    # ---- the reference's protocol --------------------------------------------------------------------------------
-    def solve(self, snowpack, emmodels, sensor, atmosphere=None, parallel_computation=None):
-        """One (snowpack, sensor configuration); `emmodels`: the per-layer instances made by Model.prepare_emmodels --
-        smrt_amd's, or any object with the reference's emmodel protocol (evaluated on the host)."""
-        from ..core.foreign import adopt_snowpack, entry_of_instance
-
-        self._check_sensor(sensor)
-        snowpack = adopt_snowpack(snowpack)
-        if atmosphere is not None or snowpack.atmosphere is not None:
-            raise SMRTError(f"the {self.NAME} solver can not handle atmosphere yet.")
-        if len(emmodels) != snowpack.nlayer:
-            raise SMRTError("one emmodel per layer is needed")
-        entries = [entry_of_instance(e, layer) for e, layer in zip(emmodels, snowpack.layers)]
-        return self.solve_batch([(sensor, snowpack)], [entries])[0]
-
-    def solve_batch(self, simulations, emmodel):
-        """simulations: sequence of (single-frequency sensor, snowpack); one Result each (see DORT.solve_batch)."""
-        from ..core.foreign import adopt_snowpack
-
-        sensors, packs, si, pi = [], [], [], []
-        seen_s, seen_p, memo = {}, {}, {}
-        for sensor, sp in simulations:
-            sp = adopt_snowpack(sp, memo)
-            si.append(seen_s.setdefault(id(sensor), len(sensors)))
-            if si[-1] == len(sensors):
-                sensors.append(sensor)
-            pi.append(seen_p.setdefault(id(sp), len(packs)))
-            if pi[-1] == len(packs):
-                packs.append(sp)
-        if not si:
-            return []
-        names = emmodel if isinstance(emmodel, (list, str)) else DORT._device_name(emmodel)
-        sol = self._solve_indexed(sensors, packs, np.asarray(si), np.asarray(pi), names)
-        return [sol.result(i) for i in range(len(si))]
-
-    def solve_plan(self, model, plan):
-        """The whole plan of a Model.run, packed once and launched once per homogeneous group."""
-        from ..core.model import nest_results
-
-        for sensor in plan.sensors:
-            self._check_sensor(sensor)
-        packer = self._packer()
-        packer._plan_facts = {id(sp): sp.layer_facts() for sp in plan.snowpacks}
-        packer._plan_model = model
-        try:
-            names = DORT.emmodel_names(model, plan, packer._plan_facts)
-            sol = self._solve_indexed(plan.sensors, plan.snowpacks, plan.sensor_index, plan.snowpack_index, names, packer)
-        finally:
-            packer._plan_facts = packer._plan_model = None
-        stacked = sol.stacked_result(plan)
-        if stacked is not None:
-            return stacked
-        return nest_results([sol.result(i) for i in range(len(plan))], plan.dimensions)
-
-    emmodel_names = DORT.emmodel_names
 
     # ---- grouping, packing, launching ----------------------------------------------------------------------------
     @classmethod
@@ -126,51 +68,32 @@ class IterativeFirstOrder(object):
         if not np.array_equal(sensor.theta_deg, sensor.theta_inc_deg):
             raise SMRTError(f"the {cls.NAME} solver computes the backscatter (theta == theta_inc)")
 
+    @staticmethod
+    def _sensor_key(sensor):
+        return tuple(np.round(sensor.theta_inc_deg, 12))
+
     def _packer(self):
         return _Packer(n_max_stream=2, m_max=0, error_handling=self.error_handling, devices=self.devices)
 
+    def _snowpack_key(self, sp, on_host):
+        self._refuse_atmosphere(sp)
+        return sp, (substrate_kind(sp.substrate), on_host)
+
     def _solve_indexed(self, sensors, packs, sens_idx, pack_idx, emmodel_names, packer=None):
-        packer = packer or self._packer()
-        sensor_keys, pack_keys = {}, {}
-        s_code = np.empty(len(sensors), np.int64)
-        for k, sensor in enumerate(sensors):
-            self._check_sensor(sensor)
-            key = tuple(np.round(sensor.theta_inc_deg, 12))
-            s_code[k] = sensor_keys.setdefault(key, len(sensor_keys))
-        p_code = np.empty(len(packs), np.int64)
-        for k, sp in enumerate(packs):
-            if sp.atmosphere is not None:
-                raise SMRTError(f"the {self.NAME} solver can not handle atmosphere yet.")
-            on_host = not isinstance(emmodel_names, str) and any(not isinstance(e, str) for e in emmodel_names[k])
-            p_code[k] = pack_keys.setdefault((substrate_kind(sp.substrate), on_host), len(pack_keys))
-        freq = np.array([float(s.frequency) for s in sensors])
-        code = s_code[sens_idx] * len(pack_keys) + p_code[pack_idx]
-        sol = self._solution(sensors, packs, sens_idx, pack_idx)
-        ctx = get_context((self.devices or [None])[0])
-        self.launches = 0
-        for g in np.unique(code):
-            sel = np.nonzero(code == g)[0]
-            u_packs, inv_p = np.unique(pack_idx[sel], return_inverse=True)
-            u_freq, inv_f = np.unique(freq[sens_idx[sel]], return_inverse=True)
-            sensor0 = sensors[sens_idx[sel[0]]]
-            sps = [packs[k] for k in u_packs]
-            names = emmodel_names if isinstance(emmodel_names, str) else [emmodel_names[k] for k in u_packs]
-            sensor_of = {float(sensors[k].frequency): sensors[k] for k in sens_idx[sel]}
-            packer.host_emmodels = None
-            batch = packer._pack(sensor0, sps, u_freq, names, sensor_of)
-            extras = self._extras(ctx.first_order_layers, batch, packer, sensor0, sps, u_freq)
-            pairs = inv_f * len(u_packs) + inv_p
-            full = len(pairs) == batch.n_pairs and np.array_equal(pairs, np.arange(batch.n_pairs))
-            out = self._run_group(ctx, batch, extras, None if full else pairs, packer, sensor0, sps, u_freq)
-            self.launches += 1
-            bad = np.nonzero(out.status != 0)[0]
-            if len(bad) and self.error_handling == "exception":
-                st = int(out.status[bad[0]])
-                raise SMRTError(STATUS_MESSAGES.get(st, f"the {self.NAME} solver failed with status {st}"))
-            sol.add_group(sel, out, (u_packs, np.array(batch.n_layers, np.int64), np.array(batch.thickness, float)),
-                          no_substrate=sps[0].substrate is None)
+        sol = SolverBase._solve_indexed(self, sensors, packs, sens_idx, pack_idx, emmodel_names, packer)
         sol.warn()
         return sol
+
+    def _prepare_group(self, ctx, g):
+        g.packer.host_emmodels = None
+        SolverBase._prepare_group(self, ctx, g)
+        g.extras = self._extras(ctx.first_order_layers, g.batch, g.packer, g.sensor0, g.sps, g.u_freq)
+
+    def _context(self):
+        return get_context((self.devices or [None])[0])   # (this module's name: the CPU tests put a stand-in here)
+
+    def _launch(self, ctx, g):
+        return self._run_group(ctx, g.batch, g.extras, g.pairs, g.packer, g.sensor0, g.sps, g.u_freq)
 
     # the two places a solver built on this one (iterative_second_order) differs in: the device call and the result axis
     def _run_group(self, ctx, batch, extras, pairs, packer, sensor0, sps, freqs):
@@ -318,23 +241,16 @@ class _Packer(DORT):
         return hl, np.zeros((F, S, Lmax), np.int32), np.zeros((F, S, Lmax, 1, 2, 6, 6))
 
 
-class _Solution:
+class _Solution(LayeredSolution):
     """Outputs of the device batches of one call, addressable per simulation and stackable as one Result."""
 
     def __init__(self, solver, sensors, packs, sens_idx, pack_idx):
-        self.solver, self.sensors, self.packs = solver, sensors, packs
-        self.sens_idx, self.pack_idx = np.asarray(sens_idx), np.asarray(pack_idx)
-        n = len(self.sens_idx)
-        self.group_of = np.full(n, -1, np.int64)
-        self.row_of = np.zeros(n, np.int64)
-        self.outputs, self.columns, self.no_substrate = [], [], []
+        LayeredSolution.__init__(self, solver, sensors, packs, sens_idx, pack_idx)
+        self.no_substrate = []
 
-    def add_group(self, sel, out, columns, no_substrate):
-        self.group_of[sel] = len(self.outputs)
-        self.row_of[sel] = np.arange(len(sel))
-        self.outputs.append(out)
-        self.columns.append(columns)
-        self.no_substrate.append(no_substrate)
+    def add_group(self, sel, out, sp0, columns=None, no_substrate=None):
+        LayeredSolution.add_group(self, sel, out, sp0, columns)
+        self.no_substrate.append(sp0.substrate is None if no_substrate is None else no_substrate)
 
     def warn(self):
         """The reference's two warnings, once per run."""
@@ -364,58 +280,25 @@ class _Solution:
         return np.concatenate([total[..., None, :, :, :], values], axis=-4)
 
     def result(self, i):
-        sensor, sp = self.sensors[self.sens_idx[i]], self.packs[self.pack_idx[i]]
+        sensor = self.sensors[self.sens_idx[i]]
         out, row = self.outputs[self.group_of[i]], self.row_of[i]
-        L = sp.nlayer
-        lay = out.layers[row][:L]
         make, labelled = result_factory(sensor)
-        layer_idx = ("layer", np.arange(L))
-        other = {
-            "effective_permittivity": labelled(lay[:, 0] + 1j * lay[:, 1], [layer_idx]),
-            "ks": labelled(lay[:, 2].copy(), [layer_idx], name="ks"),
-            "ke": labelled(lay[:, 2] + lay[:, 3], [layer_idx], name="ke"),
-            "ka": labelled(lay[:, 3].copy(), [layer_idx], name="ka"),
-            "thickness": labelled(np.asarray(sp.layer_thicknesses, float), [layer_idx], name="thickness"),
-            "backscatter_layer": labelled(out.layer_backscatter[row][:L + 1].copy(),
-                                          [("layer", np.arange(-1, L))] + self._coords(sensor)[-3:], name="backscatter_layer"),
-        }
+        other, L = self._other(i, labelled)
+        other["backscatter_layer"] = labelled(out.layer_backscatter[row][:L + 1].copy(),
+                                              [("layer", np.arange(-1, L))] + self._coords(sensor)[-3:], name="backscatter_layer")
         return make(sensor, self._values(out.values[row]), self._coords(sensor), other_data=other)
 
     def stacked_result(self, plan):
-        if len(self.outputs) != 1 or not plan.dimensions:
+        grid = self._grid(plan)
+        if grid is None:
             return None
-        sensor0 = self.sensors[0]
-        if any(s.channel_map != sensor0.channel_map for s in self.sensors[1:]):
-            return None
+        sensor0, lead, shape = grid
         out, order = self.outputs[0], self.row_of
-        lead = [(name, np.asarray(list(values))) for name, values in plan.dimensions]
-        shape = tuple(len(v) for _, v in lead)
-        if int(np.prod(shape)) != len(order):
-            return None
         values = self._values(out.values[order])
         data = LabeledArray(values.reshape(shape + values.shape[1:]), lead + self._coords(sensor0))
-        u_packs, nl_solved, thick_solved = self.columns[0]
-        slot = np.full(len(self.packs), -1, np.int64)
-        slot[u_packs] = np.arange(len(u_packs))
-        nl = nl_solved[slot[self.pack_idx]]
-        Lmax = int(nl.max())
-        lay = out.layers[order][:, :Lmax].copy()
-        below = np.arange(Lmax)[None, :] >= nl[:, None]
-        lay[below] = np.nan
-        thick = thick_solved.reshape(len(u_packs), -1)[slot[self.pack_idx], :Lmax].copy()
-        thick[below] = np.nan
+        other, nl, Lmax = self._stacked_layers(lead, shape)
         lb = out.layer_backscatter[order][:, :Lmax + 1].copy()
         lb[np.arange(Lmax + 1)[None, :] > nl[:, None]] = np.nan
-        layer_dim = [("layer", np.arange(Lmax))]
-
-        def stack(v, name=None):
-            return LabeledArray(v.reshape(shape + (Lmax,)), lead + layer_dim, name=name)
-
-        other = {
-            "effective_permittivity": stack(lay[:, :, 0] + 1j * lay[:, :, 1]),
-            "ks": stack(lay[:, :, 2], "ks"), "ke": stack(lay[:, :, 2] + lay[:, :, 3], "ke"), "ka": stack(lay[:, :, 3], "ka"),
-            "thickness": stack(thick, "thickness"),
-            "backscatter_layer": LabeledArray(lb.reshape(shape + lb.shape[1:]), lead + [("layer", np.arange(-1, Lmax))]
-                                              + self._coords(sensor0)[-3:], name="backscatter_layer"),
-        }
+        other["backscatter_layer"] = LabeledArray(lb.reshape(shape + lb.shape[1:]), lead + [("layer", np.arange(-1, Lmax))]
+                                                  + self._coords(sensor0)[-3:], name="backscatter_layer")
         return make_result(sensor0, data, other_data=other)

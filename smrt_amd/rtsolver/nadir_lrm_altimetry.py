@@ -24,7 +24,7 @@ theta_inc_sampling > 1; pitch / roll together with a surface slope.
 """
 import numpy as np
 
-from .._native import STATUS_MESSAGES, PackedLrmParams
+from .._native import PackedLrmParams
 from ..core.error import SMRTError
 from ..core.globalconstants import C_SPEED
 from ..core.result import AltimetryResult, LabeledArray
@@ -32,73 +32,40 @@ from ..core.sensor import Altimeter
 from ..interface.flat import Flat
 from ..interface.fresnel import reflection_diagonal
 from ..interface.transparent import Transparent
-from .dort import DORT, get_context
+from .dort import get_context
 from .iterative_first_order import IterativeFirstOrder, _Packer
 from .lrm_waveform_model import Brown1977  # noqa: F401  (waveform_model=Brown1977)
+from .solver_base import (LayeredSolution, SolverBase, carry_plan_facts, check_error_handling, coherent_factor, layer_permittivities,
+                          positive_integer)
 
 CONTRIBUTIONS = ["surface", "interfaces", "volume", "total"]
 
 
-class NadirLRMAltimetry(object):
+class NadirLRMAltimetry(SolverBase):
     """Options as smrt/rtsolver/nadir_lrm_altimetry.py; `devices` (list of GPU indices; the first is used) is smrt_amd's own."""
 
     _broadcast_capability = {}
+    NAME = "nadir_lrm_altimetry"
+    ATMOSPHERE = "the {} solver can not handle atmosphere."
+    CHECKS_SENSOR_FIRST = False
 
     def __init__(self, waveform_model=None, oversampling_time=10, return_oversampled=False, skip_pfs_convolution=False,
                  return_contributions=False, compute_coherent_reflection=True, theta_inc_sampling=8, error_handling="exception",
                  devices=None):
-        if error_handling not in ("exception", "nan"):
-            raise SMRTError("error_handling must be 'exception' or 'nan'")
+        check_error_handling(error_handling)
         if waveform_model is not None and getattr(waveform_model, "__name__", "") not in ("Brown1977", "brown_1977"):
             raise SMRTError("the nadir_lrm_altimetry solver offers the Brown1977 waveform model only (a model without an "
                             "analytical PFS cannot run in the reference either)")
-        if isinstance(oversampling_time, bool) or int(oversampling_time) != oversampling_time or oversampling_time < 1:
-            raise SMRTError("oversampling_time must be a positive integer")
-        if isinstance(theta_inc_sampling, bool) or int(theta_inc_sampling) != theta_inc_sampling or theta_inc_sampling < 1:
-            raise SMRTError("theta_inc_sampling must be a positive integer")
+        self.oversampling = positive_integer(oversampling_time, "oversampling_time")
+        self.theta_inc_sampling = positive_integer(theta_inc_sampling, "theta_inc_sampling")
         if skip_pfs_convolution and theta_inc_sampling > 1:
             raise SMRTError("skip_pfs_convolution is offered with theta_inc_sampling=1 only (the reference returns an array "
                             "that does not fit its coordinates otherwise)")
         self.error_handling = error_handling
-        self.oversampling = int(oversampling_time)
         self.return_oversampled, self.skip_pfs_convolution = bool(return_oversampled), bool(skip_pfs_convolution)
         self.return_contributions = bool(return_contributions)
         self.compute_coherent_reflection = bool(compute_coherent_reflection)
-        self.theta_inc_sampling = int(theta_inc_sampling)
         self.devices = devices
-        self.launches = 0   # launches of the last solve: tests assert "one launch per group"
-
-    # ---- the reference's protocol --------------------------------------------------------------------------------
-    def solve(self, snowpack, emmodels, sensor, atmosphere=None, parallel_computation=None):
-        from ..core.foreign import adopt_snowpack, entry_of_instance
-
-        snowpack = adopt_snowpack(snowpack)
-        if atmosphere is not None:
-            raise SMRTError("the nadir_lrm_altimetry solver can not handle atmosphere.")
-        if len(emmodels) != snowpack.nlayer:
-            raise SMRTError("one emmodel per layer is needed")
-        entries = [entry_of_instance(e, layer) for e, layer in zip(emmodels, snowpack.layers)]
-        return self.solve_batch([(sensor, snowpack)], [entries])[0]
-
-    solve_batch = IterativeFirstOrder.solve_batch
-    emmodel_names = DORT.emmodel_names
-
-    def solve_plan(self, model, plan):
-        """The whole plan of a Model.run, packed once and launched once per group."""
-        from ..core.model import nest_results
-
-        packer = self._packer()
-        packer._plan_facts = {id(sp): sp.layer_facts() for sp in plan.snowpacks}
-        packer._plan_model = model
-        try:
-            names = DORT.emmodel_names(model, plan, packer._plan_facts)
-            sol = self._solve_indexed(plan.sensors, plan.snowpacks, plan.sensor_index, plan.snowpack_index, names, packer)
-        finally:
-            packer._plan_facts = packer._plan_model = None
-        stacked = sol.stacked_result(plan)
-        if stacked is not None:
-            return stacked
-        return nest_results([sol.result(i) for i in range(len(plan))], plan.dimensions)
 
     # ---- checks ------------------------------------------------------------------------------------------------------
     def _check_sensor(self, sensor):
@@ -120,8 +87,7 @@ class NadirLRMAltimetry(object):
             raise SMRTError("The number 'theta_inc_sampling' must be a true divider of the number of gates.")
 
     def _check_snowpack(self, sp, sensor):
-        if sp.atmosphere is not None:
-            raise SMRTError("the nadir_lrm_altimetry solver can not handle atmosphere.")
+        self._refuse_atmosphere(sp)
         sigma, slope = float(getattr(sp, "sigma_surface", 0) or 0), float(getattr(sp, "surface_slope", 0) or 0)
         if self.theta_inc_sampling > 1 and sigma > 0:
             raise SMRTError("theta_inc_sampling > 1 can not be combined with sigma_surface > 0 (the reference reads a pulse_sigma "
@@ -149,51 +115,34 @@ class NadirLRMAltimetry(object):
         return np.zeros(1)
 
     # ---- grouping, packing, launching ----------------------------------------------------------------------------
-    def _solve_indexed(self, sensors, packs, sens_idx, pack_idx, emmodel_names, packer=None):
-        packer = packer or self._packer()
-        keys = {}
-        s_code = np.empty(len(sensors), np.int64)
-        for k, sensor in enumerate(sensors):
-            self._check_sensor(sensor)
-            key = tuple(float(getattr(sensor, a)) for a in ("altitude", "pulse_bandwidth", "beamwidth_alongtrack", "beamwidth_acrosstrack",
-                                                            "antenna_gain", "ngate", "nominal_gate", "pitch_angle", "roll_angle"))
-            s_code[k] = keys.setdefault(key, len(keys))
-        on_host = np.array([not isinstance(emmodel_names, str) and any(not isinstance(e, str) for e in emmodel_names[k])
-                            for k in range(len(packs))], np.int64)
-        freq = np.array([float(s.frequency) for s in sensors])
-        code = s_code[sens_idx] * 2 + on_host[pack_idx]
-        sol = _Solution(self, sensors, packs, sens_idx, pack_idx)
-        ctx = get_context((self.devices or [None])[0])
-        self.launches = 0
-        for g in np.unique(code):
-            sel = np.nonzero(code == g)[0]
-            u_packs, inv_p = np.unique(pack_idx[sel], return_inverse=True)
-            u_freq, inv_f = np.unique(freq[sens_idx[sel]], return_inverse=True)
-            sensor0 = sensors[sens_idx[sel[0]]]
-            sps = [packs[k] for k in u_packs]
-            surf = np.array([self._check_snowpack(sp, sensor0) for sp in sps])
-            names = emmodel_names if isinstance(emmodel_names, str) else [emmodel_names[k] for k in u_packs]
-            sensor_of = {float(sensors[k].frequency): sensors[k] for k in sens_idx[sel]}
-            packer.host_emmodels = None
-            bare = [sp if sp.substrate is None else _without_substrate(sp, packer) for sp in sps]
-            batch = packer._pack(sensor0, bare, u_freq, names, sensor_of)
-            t_inc = self._t_inc(sensor0)
-            options = dict(oversampling=self.oversampling, t_inc=t_inc, return_contributions=self.return_contributions,
-                           return_oversampled=self.return_oversampled, skip_pfs_convolution=self.skip_pfs_convolution,
-                           sigma_surface=surf[:, 0] if surf[:, 0].any() else None, surface_slope=surf[:, 1] if surf[:, 1].any() else None)
-            itf = self._interface_values(ctx, batch, packer, sensor0, sps, u_freq, t_inc, options)
-            params = PackedLrmParams(sensor0, interface_values=itf, **options)
-            pairs = inv_f * len(u_packs) + inv_p
-            full = len(pairs) == batch.n_pairs and np.array_equal(pairs, np.arange(batch.n_pairs))
-            with ctx.lock:
-                out = ctx.lrm_run(batch, params, pairs=None if full else pairs)
-            self.launches += 1
-            bad = np.nonzero(out.status != 0)[0]
-            if len(bad) and self.error_handling == "exception":
-                st = int(out.status[bad[0]])
-                raise SMRTError(STATUS_MESSAGES.get(st, f"the nadir_lrm_altimetry solver failed with status {st}"))
-            sol.add_group(sel, out, (u_packs, np.array(batch.n_layers, np.int64), np.array(batch.thickness, float)))
-        return sol
+    @staticmethod
+    def _sensor_key(sensor):
+        return tuple(float(getattr(sensor, a)) for a in ("altitude", "pulse_bandwidth", "beamwidth_alongtrack", "beamwidth_acrosstrack",
+                                                         "antenna_gain", "ngate", "nominal_gate", "pitch_angle", "roll_angle"))
+
+    def _snowpack_key(self, sp, on_host):
+        return sp, on_host    # (checked per group: what is refused depends on the sensor)
+
+    def _context(self):
+        return get_context((self.devices or [None])[0])   # (this module's name: the CPU tests put a stand-in here)
+
+    def _solution(self, sensors, packs, sens_idx, pack_idx):
+        return _Solution(self, sensors, packs, sens_idx, pack_idx)
+
+    def _prepare_group(self, ctx, g):
+        surf = np.array([self._check_snowpack(sp, g.sensor0) for sp in g.sps])
+        g.packer.host_emmodels = None
+        bare = [sp if sp.substrate is None else _without_substrate(sp, g.packer) for sp in g.sps]
+        g.batch = g.packer._pack(g.sensor0, bare, g.u_freq, g.names, g.sensor_of)
+        t_inc = self._t_inc(g.sensor0)
+        options = dict(oversampling=self.oversampling, t_inc=t_inc, return_contributions=self.return_contributions,
+                       return_oversampled=self.return_oversampled, skip_pfs_convolution=self.skip_pfs_convolution,
+                       sigma_surface=surf[:, 0] if surf[:, 0].any() else None, surface_slope=surf[:, 1] if surf[:, 1].any() else None)
+        itf = self._interface_values(ctx, g.batch, g.packer, g.sensor0, g.sps, g.u_freq, t_inc, options)
+        g.params = PackedLrmParams(g.sensor0, interface_values=itf, **options)
+
+    def _launch(self, ctx, g):
+        return ctx.lrm_run(g.batch, g.params, pairs=g.pairs)
 
     # ---- what the host evaluates (include/smrt_dort.h: smrt_lrm_params.interface_values) ----------------------------
     def _interface_values(self, ctx, batch, packer, sensor0, sps, freqs, t_inc, options):
@@ -205,12 +154,8 @@ class NadirLRMAltimetry(object):
         if all(on_device(i) for sp in sps for i in sp.interfaces) and all(sp.substrate is None for sp in sps):
             return None
         F, S, Lmax, n_mu = len(freqs), len(sps), int(batch.struct.n_layers_max), len(t_inc)
-        if packer.host_emmodels is not None:
-            eps = batch.host_layer.reshape(F, S, Lmax, 4)[..., 2]
-        else:   # the device's own permittivities: the (pair, layer) kernel alone, not a launch of the solver
-            with ctx.lock:
-                layers = ctx.lrm_layers(batch, PackedLrmParams(sensor0, **dict(options, sigma_surface=None, surface_slope=None)))
-            eps = np.asarray(layers).reshape(F, S, Lmax, 5)[..., 0]
+        params = None if packer.host_emmodels is not None else PackedLrmParams(sensor0, **dict(options, sigma_surface=None, surface_slope=None))
+        eps = layer_permittivities(ctx, batch, packer, params)[..., 0].reshape(F, S, Lmax)   # (the real part: DESIGN.md 4h)
         mu_i = 1.0 / (1.0 + C_SPEED * t_inc / sensor0.altitude) if n_mu > 1 else np.ones(1)
         mu_i = mu_i * np.cos(sensor0.pitch_angle) * np.cos(sensor0.roll_angle)
         values = np.zeros((F, S, Lmax + 1, 1 + n_mu))
@@ -245,10 +190,7 @@ class NadirLRMAltimetry(object):
         if self.compute_coherent_reflection and hasattr(obj, "roughness_rms"):
             below = complex(obj.permittivity(frequency)) if substrate else eps_2
             specular = np.asarray(reflection_diagonal(eps_1, below, mu, 2), float)[0]
-            beta0 = np.sqrt(C_SPEED / (sensor.pulse_bandwidth * sensor.altitude)) * np.sqrt(2)
-            beta12 = 1 / (wavenumber * sensor.altitude * beta0) ** 2 + beta0 ** 2 / 4
-            factor = np.exp(-4 * (wavenumber * obj.roughness_rms) ** 2 - (1 - mu ** 2) / beta12) / beta12 / (4 * np.pi)
-            echo = echo + specular * factor
+            echo = echo + specular * coherent_factor(sensor, wavenumber, obj.roughness_rms, mu)
         return echo
 
 
@@ -257,26 +199,15 @@ def _without_substrate(sp, packer):
     from ..core.snowpack import Snowpack
 
     bare = Snowpack(layers=sp.layers, interfaces=[Flat() for _ in sp.layers])
-    if packer._plan_facts is not None:
-        packer._plan_facts[id(bare)] = packer._plan_facts.get(id(sp))
+    carry_plan_facts(packer, sp, bare)
     return bare
 
 
-class _Solution:
-    """Outputs of the device batches of one call, addressable per simulation and stackable as one result."""
+class _Solution(LayeredSolution):
+    """Outputs of the device batches of one call, addressable per simulation and stackable as one result.  The SAR solver's
+    (rtsolver/nadir_sar_altimetry.py) differs in the coordinates alone: what it replaces is marked."""
 
-    def __init__(self, solver, sensors, packs, sens_idx, pack_idx):
-        self.solver, self.sensors, self.packs = solver, sensors, packs
-        self.sens_idx, self.pack_idx = np.asarray(sens_idx), np.asarray(pack_idx)
-        n = len(self.sens_idx)
-        self.group_of, self.row_of = np.full(n, -1, np.int64), np.zeros(n, np.int64)
-        self.outputs, self.columns = [], []
-
-    def add_group(self, sel, out, columns):
-        self.group_of[sel] = len(self.outputs)
-        self.row_of[sel] = np.arange(len(sel))
-        self.outputs.append(out)
-        self.columns.append(columns)
+    LAYER_EXTRA = ("backward_scattering",)
 
     def _delay(self, sensor):
         so = self.solver
@@ -285,17 +216,29 @@ class _Solution:
             t_gate = t_gate[::so.oversampling]
         return t_gate - sensor.nominal_gate / sensor.pulse_bandwidth
 
-    def _coords(self, sensor):
+    def _coords(self, sensor, n_boundaries=None):   # (replaced)
         coords = [("delay", self._delay(sensor)), ("theta_inc", [0]), ("theta", [0])]
         return ([("contribution", CONTRIBUTIONS)] if self.solver.return_contributions else []) + coords
 
-    def _values(self, values):
+    def _values(self, values, n_boundaries=None):   # (replaced)
         """[..., rows, n] -> [..., n, 1, 1], or [..., 4, n, 1, 1] with the total last."""
         if self.solver.return_contributions:
             values = np.concatenate([values, np.sum(values, axis=-2)[..., None, :]], axis=-2)
         else:
             values = values[..., 0, :]
         return values[..., None, None]
+
+    def _n_boundaries(self, out, slot):   # (replaced: the SAR solver's contributions depend on the boundaries of the snowpack)
+        return None
+
+    def _stackable(self, n_boundaries):   # (replaced)
+        return True
+
+    def _z_coord(self, sensor, foreign=False):   # (replaced)
+        return ("delay", self._delay(sensor))
+
+    def _foreign_coords(self, sensor):   # (extended)
+        return dict(gate=("delay", self._delay(sensor) * sensor.pulse_bandwidth + sensor.nominal_gate))
 
     @staticmethod
     def _attrs(sensor):
@@ -323,66 +266,36 @@ class _Solution:
         return (cls, labelled) if cls is not None else None
 
     def result(self, i):
-        sensor, sp = self.sensors[self.sens_idx[i]], self.packs[self.pack_idx[i]]
-        out, row = self.outputs[self.group_of[i]], self.row_of[i]
-        L = sp.nlayer
-        lay = out.layers[row][:L]
-        layer_idx = ("layer", np.arange(L))
-        other = {
-            "effective_permittivity": LabeledArray(lay[:, 0] + 1j * lay[:, 1], [layer_idx]),
-            "ks": LabeledArray(lay[:, 2].copy(), [layer_idx], name="ks"),
-            "ke": LabeledArray(lay[:, 2] + lay[:, 3], [layer_idx], name="ke"),
-            "ka": LabeledArray(lay[:, 3].copy(), [layer_idx], name="ka"),
-            "backward_scattering": LabeledArray(lay[:, 4].copy(), [layer_idx], name="backward_scattering"),
-            "thickness": LabeledArray(np.asarray(sp.layer_thicknesses, float), [layer_idx], name="thickness"),
-        }
-        coords = self._coords(sensor)
+        sensor, group = self.sensors[self.sens_idx[i]], self.group_of[i]
+        out, row = self.outputs[group], self.row_of[i]
+        nb = self._n_boundaries(out, self._slot(group, self.pack_idx[i]))
+        other, _ = self._other(i)   # (the layers as solved: the SAR solver prunes)
+        coords = self._coords(sensor, nb)
+        values = self._values(out.values[row], nb)
         foreign = self._foreign(sensor)
         if foreign is not None:   # as the reference builds it: the gate as a coordinate of delay where xarray can, z_gate an attribute
             cls, labelled = foreign
-            data = labelled(self._values(out.values[row]), coords)
+            data = labelled(values, coords)
             if hasattr(data, "assign_coords"):
-                data = data.assign_coords(gate=("delay", coords[-3][1] * sensor.pulse_bandwidth + sensor.nominal_gate))
+                data = data.assign_coords(**self._foreign_coords(sensor))
             res = cls(data, channel_map=sensor.channel_map,
                       other_data={k: labelled(v.values, list(v.coords.items()), name=v.name) for k, v in other.items()})
-            res.z_gate = labelled(out.z_gate[row].copy(), [coords[-3]], name="z_gate")
+            res.z_gate = labelled(out.z_gate[row].copy(), [self._z_coord(sensor, foreign=True)], name="z_gate")
             return res
-        z_gate = LabeledArray(out.z_gate[row].copy(), [coords[-3]], name="z_gate")
-        return self._result(sensor, LabeledArray(self._values(out.values[row]), coords), z_gate, other)
+        z_gate = LabeledArray(out.z_gate[row].copy(), [self._z_coord(sensor)], name="z_gate")
+        return self._result(sensor, LabeledArray(values, coords), z_gate, other)
 
     def stacked_result(self, plan):
-        if len(self.outputs) != 1 or not plan.dimensions:
+        grid = self._grid(plan)
+        if grid is None or self._foreign(grid[0]) is not None:
             return None
-        sensor0 = self.sensors[0]
-        if any(s.channel_map != sensor0.channel_map for s in self.sensors[1:]) or self._foreign(sensor0) is not None:
-            return None
+        sensor0, lead, shape = grid
         out, order = self.outputs[0], self.row_of
-        lead = [(name, np.asarray(list(values))) for name, values in plan.dimensions]
-        shape = tuple(len(v) for _, v in lead)
-        if int(np.prod(shape)) != len(order):
+        nbs = self._n_boundaries(out, self._slot(0, self.pack_idx))
+        if not self._stackable(nbs):
             return None
-        values = self._values(out.values[order])
-        coords = self._coords(sensor0)
-        data = LabeledArray(values.reshape(shape + values.shape[1:]), lead + coords)
-        z_gate = LabeledArray(out.z_gate[order].reshape(shape + (-1,)), lead + [coords[-3]], name="z_gate")
-        u_packs, nl_solved, thick_solved = self.columns[0]
-        slot = np.full(len(self.packs), -1, np.int64)
-        slot[u_packs] = np.arange(len(u_packs))
-        nl = nl_solved[slot[self.pack_idx]]
-        Lmax = int(nl.max())
-        lay = out.layers[order][:, :Lmax].copy()
-        below = np.arange(Lmax)[None, :] >= nl[:, None]
-        lay[below] = np.nan
-        thick = thick_solved.reshape(len(u_packs), -1)[slot[self.pack_idx], :Lmax].copy()
-        thick[below] = np.nan
-        layer_dim = [("layer", np.arange(Lmax))]
-
-        def stack(v, name=None):
-            return LabeledArray(v.reshape(shape + (Lmax,)), lead + layer_dim, name=name)
-
-        other = {
-            "effective_permittivity": stack(lay[:, :, 0] + 1j * lay[:, :, 1]),
-            "ks": stack(lay[:, :, 2], "ks"), "ke": stack(lay[:, :, 2] + lay[:, :, 3], "ke"), "ka": stack(lay[:, :, 3], "ka"),
-            "backward_scattering": stack(lay[:, :, 4], "backward_scattering"), "thickness": stack(thick, "thickness"),
-        }
-        return self._result(sensor0, data, z_gate, other)
+        nb = None if nbs is None else int(nbs[0])
+        values = self._values(out.values[order], nb)
+        data = LabeledArray(values.reshape(shape + values.shape[1:]), lead + self._coords(sensor0, nb))
+        z_gate = LabeledArray(out.z_gate[order].reshape(shape + (-1,)), lead + [self._z_coord(sensor0)], name="z_gate")
+        return self._result(sensor0, data, z_gate, self._stacked_layers(lead, shape)[0])

@@ -32,10 +32,9 @@ ndoppler; a boundary with a positive echo later than the window.  Of smrt_amd's 
 """
 import numpy as np
 
-from .._native import STATUS_MESSAGES, PackedLrmParams, PackedSarParams, ptr_gaussian_approximation
+from .._native import PackedLrmParams, PackedSarParams, ptr_gaussian_approximation
 from ..core.error import SMRTError, smrt_warn
 from ..core.globalconstants import C_SPEED
-from ..core.result import LabeledArray
 from ..core.sensor import Altimeter
 from ..core.terrain import TerrainInfo
 from ..interface.fresnel import reflection_diagonal
@@ -44,6 +43,7 @@ from .delay_doppler_model.halimi14 import Halimi14  # noqa: F401  (delay_doppler
 from .dort import get_context
 from .iterative_first_order import IterativeFirstOrder
 from .nadir_lrm_altimetry import NadirLRMAltimetry, _Solution as _LrmSolution, _without_substrate
+from .solver_base import SolverBase, check_error_handling, coherent_factor, layer_permittivities, positive_integer
 
 OUTPUT_BUDGET = 1 << 30   # bytes of the maps and of the f0 / f1 tables of one launch
 
@@ -52,12 +52,12 @@ class NadirSARAltimetry(NadirLRMAltimetry):
     """Options as smrt/rtsolver/nadir_sar_altimetry.py; `devices` (list of GPU indices; the first is used) is smrt_amd's own."""
 
     _broadcast_capability = {}
+    NAME = "nadir_sar_altimetry"
 
     def __init__(self, delay_doppler_model=None, delay_doppler_model_options=None, oversampling_time=4, oversampling_doppler=4,
                  return_oversampled=False, skip_convolutions=False, return_contributions=False, theta_inc_sampling=8,
                  error_handling="exception", prune_deep_snowpack=True, devices=None):
-        if error_handling not in ("exception", "nan"):
-            raise SMRTError("error_handling must be 'exception' or 'nan'")
+        check_error_handling(error_handling)
         name = delay_doppler_model if isinstance(delay_doppler_model, str) else getattr(delay_doppler_model, "__name__", None)
         model = "dinardo18" if delay_doppler_model is None else (name or "").lower()
         if model not in ("dinardo18", "halimi14"):
@@ -75,10 +75,8 @@ class NadirSARAltimetry(NadirLRMAltimetry):
             for what in ("ptr_time", "ptr_doppler"):
                 if options.get(what) not in (None, "sinc^2"):
                     raise SMRTError(f"Halimi14 takes {what}=None or 'sinc^2' only (as the reference, which raises NotImplementedError)")
-            widening = options.get("delay_window_widening", 1)
-            if isinstance(widening, bool) or not isinstance(widening, (int, np.integer)) or widening < 1:
-                raise SMRTError("delay_window_widening must be a positive integer")
-            self.slant_range_correction, self.delay_window_widening = bool(options.get("slant_range_correction", True)), int(widening)
+            self.delay_window_widening = positive_integer(options.get("delay_window_widening", 1), "delay_window_widening")
+            self.slant_range_correction = bool(options.get("slant_range_correction", True))
         else:
             unknown = set(options) - {"ptr_time", "ptr_doppler", "oversampling_time", "oversampling_doppler"}
             if unknown:
@@ -86,9 +84,8 @@ class NadirSARAltimetry(NadirLRMAltimetry):
             if not (options.get("ptr_time") or "gaussian").startswith("gaussian"):
                 raise SMRTError("Dinardo18 takes a Gaussian ptr_time only")
             self.ptr_doppler = options.get("ptr_doppler", "gaussian-smrt")
-        for what, value in (("oversampling_time", oversampling_time), ("oversampling_doppler", oversampling_doppler)):
-            if isinstance(value, bool) or int(value) != value or value < 1:
-                raise SMRTError(what + " must be a positive integer")
+        self.oversampling_time = positive_integer(oversampling_time, "oversampling_time")
+        self.oversampling_doppler = positive_integer(oversampling_doppler, "oversampling_doppler")
         if skip_convolutions:
             raise SMRTError("skip_convolutions is not implemented (nor in the reference)")
         if return_contributions is True:
@@ -100,12 +97,10 @@ class NadirSARAltimetry(NadirLRMAltimetry):
         self.return_coherent = return_contributions.endswith(" coherent")
         self.return_contributions = return_contributions.replace(" coherent", "")
         self.error_handling = error_handling
-        self.oversampling_time, self.oversampling_doppler = int(oversampling_time), int(oversampling_doppler)
         self.return_oversampled, self.skip_convolutions = bool(return_oversampled), False
         self.theta_inc_sampling = theta_inc_sampling   # (the geometrical-optics branch evaluates nadir only)
         self.prune_deep_snowpack = bool(prune_deep_snowpack)
         self.devices = devices
-        self.launches = 0   # launches of the last solve: tests assert "one launch per group"
 
     # ---- checks ------------------------------------------------------------------------------------------------------
     def _check_sensor(self, sensor):
@@ -124,8 +119,7 @@ class NadirSARAltimetry(NadirLRMAltimetry):
             ptr_gaussian_approximation(self.ptr_doppler, sensor.doppler_window)
 
     def _check_snowpack(self, sp, sensor=None):
-        if sp.atmosphere is not None:
-            raise SMRTError("the nadir_sar_altimetry solver can not handle atmosphere.")
+        self._refuse_atmosphere(sp)
         info = getattr(sp, "terrain_info", None)
         info = TerrainInfo() if info is None else info
         model = "Halimi14" if self.delay_doppler_model == "halimi14" else "Dinardo18"
@@ -178,106 +172,91 @@ class NadirSARAltimetry(NadirLRMAltimetry):
         return [f"interface {i}" for i in range(nb)] + ["volume", "total"], list(range(nb)) + [-1] * nb + [nb, nb + 1]
 
     # ---- grouping, packing, launching ----------------------------------------------------------------------------
-    def _solve_indexed(self, sensors, packs, sens_idx, pack_idx, emmodel_names, packer=None):
-        packer = packer or self._packer()
-        keys = {}
-        s_code = np.empty(len(sensors), np.int64)
-        for k, sensor in enumerate(sensors):
-            self._check_sensor(sensor)
-            key = tuple(float(getattr(sensor, a)) for a in (
-                "frequency", "altitude", "pulse_bandwidth", "beamwidth_alongtrack", "beamwidth_acrosstrack", "antenna_gain", "ngate",
-                "ndoppler", "nominal_gate", "pitch_angle", "roll_angle", "velocity", "pulse_repetition_frequency")) + (
-                    sensor.doppler_window, self.delay_doppler_model, self.slant_range_correction, self.delay_window_widening)
-            s_code[k] = keys.setdefault(key, len(keys))
-        on_host = np.array([not isinstance(emmodel_names, str) and any(not isinstance(e, str) for e in emmodel_names[k])
-                            for k in range(len(packs))], np.int64)
-        sens_idx, pack_idx = np.asarray(sens_idx), np.asarray(pack_idx)
-        code = s_code[sens_idx] * 2 + on_host[pack_idx]
-        sol = _Solution(self, sensors, packs, sens_idx, pack_idx)
-        ctx = get_context((self.devices or [None])[0])
-        self.launches = 0
-        for g in np.unique(code):
-            sel = np.nonzero(code == g)[0]
-            u_packs, inv_p = np.unique(pack_idx[sel], return_inverse=True)
-            sensor0 = sensors[sens_idx[sel[0]]]
-            sigma = np.array([self._check_snowpack(packs[k]) for k in u_packs])
-            sps = [self._pruned(packs[k], sensor0) for k in u_packs]
-            if isinstance(emmodel_names, str):
-                names = emmodel_names
-            else:
-                names = [list(emmodel_names[k])[:sp.nlayer] for k, sp in zip(u_packs, sps)]
-            packer.host_emmodels = None
-            bare = [_without_substrate(sp, packer) for sp in sps]
-            for b, sp in zip(bare, sps):   # (a pruned snowpack is new to the plan: it has the facts of no snowpack of it)
-                if packer._plan_facts is not None and packer._plan_facts.get(id(b)) is None:
-                    packer._plan_facts[id(b)] = b.layer_facts()
-            freq = np.array([float(sensor0.frequency)])
-            batch = packer._pack(sensor0, bare, freq, names, {float(sensor0.frequency): sensor0})
-            Lmax = int(batch.struct.n_layers_max)
-            values = self._boundary_values(ctx, batch, packer, sensor0, sps, Lmax)
-            row_map = np.full((len(sps), 2 * (Lmax + 1) + 2), -1, np.int32)
-            n_rows = 1
-            for s, sp in enumerate(sps):
-                nb = _n_boundaries(sp)
-                names_s, rows = self.contributions(nb)
-                row_map[s, :nb], row_map[s, Lmax + 1:Lmax + 1 + nb], row_map[s, -2:] = rows[:nb], rows[nb:2 * nb], rows[-2:]
-                n_rows = max(n_rows, len(names_s), 1)
-            pairs = np.asarray(inv_p, np.int64)
-            # A part of the group holds its maps AND the tables of its own distinct sigma_surface (at worst one pair of tables
-            # per snowpack) inside the budget.
-            fine = sensor0.ngate * self.oversampling_time * sensor0.ndoppler * self.oversampling_doppler
-            per_pair = n_rows * (fine if self.return_oversampled else sensor0.ngate * sensor0.ndoppler) * 8
-            n_sigma = len(np.unique(sigma))
-            # (Dinardo18: f0 and f1 per sigma_surface.  Halimi14: one table per sigma_surface, and once per launch the impulse
-            # response convolved along Doppler on the widened window)
-            halimi = self.delay_doppler_model == "halimi14"
-            table, fixed = (fine * 8, fine * self.delay_window_widening * 8) if halimi else (2 * fine * 8, 0)
-            step = max(1, (OUTPUT_BUDGET - fixed - min(n_sigma, len(pairs)) * table) // per_pair)
-            if step < len(pairs):   # (several parts: each with at most `step` tables of its own)
-                step = max(1, (OUTPUT_BUDGET - fixed) // (per_pair + table))
-            outs = []
-            for begin in range(0, len(pairs), step):
-                part = pairs[begin:begin + step]
-                full = len(part) == batch.n_pairs and np.array_equal(part, np.arange(batch.n_pairs))
-                table_sigma, index = np.unique(sigma[part], return_inverse=True)
-                table_index = np.zeros(len(sps), np.int32)      # (a snowpack outside the part is not read)
-                table_index[part] = index
-                params = PackedSarParams(sensor0, table_sigma, table_index, values, row_map, n_rows=n_rows,
-                                         oversampling_time=self.oversampling_time, oversampling_doppler=self.oversampling_doppler,
-                                         return_oversampled=self.return_oversampled, ptr_doppler=self.ptr_doppler,
-                                         model=self.delay_doppler_model, slant_range_correction=self.slant_range_correction,
-                                         delay_window_widening=self.delay_window_widening)
-                with ctx.lock:
-                    outs.append(ctx.sar_run(batch, params, pairs=None if full else part))
-                self.launches += 1
-            out = outs[0] if len(outs) == 1 else _joined(outs)
-            bad = np.nonzero(out.status != 0)[0]
-            if len(bad) and self.error_handling == "exception":
-                st = int(out.status[bad[0]])
-                late = np.isfinite(out.echo[bad[0]]).all()
-                raise SMRTError("a boundary with a positive echo lies later than the window of the altimeter (the reference fails on "
-                                "`0 <= itime < N`): use fewer layers, or a sensor with more gates" if late else
-                                STATUS_MESSAGES.get(st, f"the nadir_sar_altimetry solver failed with status {st}"))
-            sol.add_group(sel, out, (u_packs, np.array(batch.n_layers, np.int64), np.array(batch.thickness, float),
-                                     np.array([_n_boundaries(sp) for sp in sps], np.int64)))
-        return sol
+    def _sensor_key(self, sensor):
+        return tuple(float(getattr(sensor, a)) for a in (
+            "frequency", "altitude", "pulse_bandwidth", "beamwidth_alongtrack", "beamwidth_acrosstrack", "antenna_gain", "ngate",
+            "ndoppler", "nominal_gate", "pitch_angle", "roll_angle", "velocity", "pulse_repetition_frequency")) + (
+                sensor.doppler_window, self.delay_doppler_model, self.slant_range_correction, self.delay_window_widening)
+
+    def _context(self):
+        return get_context((self.devices or [None])[0])   # (this module's name: the CPU tests put a stand-in here)
+
+    def _solution(self, sensors, packs, sens_idx, pack_idx):
+        return _Solution(self, sensors, packs, sens_idx, pack_idx)
+
+    def _prepare_group(self, ctx, g):
+        """Packs the snowpacks the reference solves (_pruned) and evaluates their boundaries; sets g.sigma, g.values, g.row_map
+        and g.n_rows for the launch."""
+        sensor0, packer = g.sensor0, g.packer
+        g.sigma = np.array([self._check_snowpack(sp) for sp in g.sps])
+        g.sps = sps = [self._pruned(sp, sensor0) for sp in g.sps]
+        if not isinstance(g.names, str):
+            g.names = [list(names)[:sp.nlayer] for names, sp in zip(g.names, sps)]
+        packer.host_emmodels = None
+        bare = [_without_substrate(sp, packer) for sp in sps]
+        for b, sp in zip(bare, sps):   # (a pruned snowpack is new to the plan: it has the facts of no snowpack of it)
+            if packer._plan_facts is not None and packer._plan_facts.get(id(b)) is None:
+                packer._plan_facts[id(b)] = b.layer_facts()
+        g.batch = packer._pack(sensor0, bare, g.u_freq, g.names, g.sensor_of)   # (one frequency: it is part of the sensor key)
+        Lmax = int(g.batch.struct.n_layers_max)
+        g.values = self._boundary_values(ctx, g.batch, packer, sensor0, sps, Lmax)
+        g.row_map = np.full((len(sps), 2 * (Lmax + 1) + 2), -1, np.int32)
+        g.n_rows = 1
+        for s, sp in enumerate(sps):
+            nb = _n_boundaries(sp)
+            names_s, rows = self.contributions(nb)
+            g.row_map[s, :nb], g.row_map[s, Lmax + 1:Lmax + 1 + nb], g.row_map[s, -2:] = rows[:nb], rows[nb:2 * nb], rows[-2:]
+            g.n_rows = max(g.n_rows, len(names_s), 1)
+
+    def _launch(self, ctx, g):
+        """The pairs of the group in as many parts as OUTPUT_BUDGET asks for, their outputs as one."""
+        sensor0, sigma, n_rows = g.sensor0, g.sigma, g.n_rows
+        pairs = np.asarray(g.pair_of_row, np.int64)
+        # A part of the group holds its maps AND the tables of its own distinct sigma_surface (at worst one pair of tables
+        # per snowpack) inside the budget.
+        fine = sensor0.ngate * self.oversampling_time * sensor0.ndoppler * self.oversampling_doppler
+        per_pair = n_rows * (fine if self.return_oversampled else sensor0.ngate * sensor0.ndoppler) * 8
+        n_sigma = len(np.unique(sigma))
+        # (Dinardo18: f0 and f1 per sigma_surface.  Halimi14: one table per sigma_surface, and once per launch the impulse
+        # response convolved along Doppler on the widened window)
+        halimi = self.delay_doppler_model == "halimi14"
+        table, fixed = (fine * 8, fine * self.delay_window_widening * 8) if halimi else (2 * fine * 8, 0)
+        step = max(1, (OUTPUT_BUDGET - fixed - min(n_sigma, len(pairs)) * table) // per_pair)
+        if step < len(pairs):   # (several parts: each with at most `step` tables of its own)
+            step = max(1, (OUTPUT_BUDGET - fixed) // (per_pair + table))
+        outs = []
+        for begin in range(0, len(pairs), step):
+            part = pairs[begin:begin + step]
+            full = len(part) == g.batch.n_pairs and np.array_equal(part, np.arange(g.batch.n_pairs))
+            table_sigma, index = np.unique(sigma[part], return_inverse=True)
+            table_index = np.zeros(len(g.sps), np.int32)      # (a snowpack outside the part is not read)
+            table_index[part] = index
+            params = PackedSarParams(sensor0, table_sigma, table_index, g.values, g.row_map, n_rows=n_rows,
+                                     oversampling_time=self.oversampling_time, oversampling_doppler=self.oversampling_doppler,
+                                     return_oversampled=self.return_oversampled, ptr_doppler=self.ptr_doppler,
+                                     model=self.delay_doppler_model, slant_range_correction=self.slant_range_correction,
+                                     delay_window_widening=self.delay_window_widening)
+            outs.append(ctx.sar_run(g.batch, params, pairs=None if full else part))
+        self.launches += len(outs) - 1   # (the group loop counts one)
+        out = outs[0] if len(outs) == 1 else _joined(outs)
+        out.n_boundaries = np.array([_n_boundaries(sp) for sp in g.sps], np.int64)   # (per snowpack of the batch, after pruning)
+        return out
+
+    def _status_message(self, out, at, status):
+        if np.isfinite(out.echo[at]).all():
+            return ("a boundary with a positive echo lies later than the window of the altimeter (the reference fails on "
+                    "`0 <= itime < N`): use fewer layers, or a sensor with more gates")
+        return SolverBase._status_message(self, out, at, status)
 
     # ---- what the host evaluates (include/smrt_dort.h: smrt_sar_params.boundary_values) ------------------------------
     def _boundary_values(self, ctx, batch, packer, sensor0, sps, Lmax):
         """[S, Lmax + 1, 4]: the one-way transmission at nadir, the coherent and the incoherent echo at the local incidence of the
         (mis-pointed) antenna, one over the mean square slope."""
         S, f = len(sps), float(sensor0.frequency)
-        if packer.host_emmodels is not None:
-            h = batch.host_layer.reshape(S, Lmax, 4)
-            eps = h[..., 2] + 1j * h[..., 3]
-        else:   # the device's own permittivities: the (pair, layer) kernel alone, not a launch of the solver
-            with ctx.lock:
-                layers = np.asarray(ctx.lrm_layers(batch, PackedLrmParams(sensor0))).reshape(S, Lmax, 5)
-            eps = layers[..., 0] + 1j * layers[..., 1]
+        eps = layer_permittivities(ctx, batch, packer, None if packer.host_emmodels is not None else PackedLrmParams(sensor0))
+        eps = eps[..., 0] + 1j * eps[..., 1]   # (the complex value: DESIGN.md 4h)
         mu_i = np.ones(1) * np.cos(sensor0.pitch_angle) * np.cos(sensor0.roll_angle)
         wavenumber = 2 * np.pi * f / C_SPEED
-        beta0 = np.sqrt(C_SPEED / (sensor0.pulse_bandwidth * sensor0.altitude)) * np.sqrt(2)
-        beta12 = 1 / (wavenumber * sensor0.altitude * beta0) ** 2 + beta0 ** 2 / 4
         values = np.zeros((S, Lmax + 1, 4))
         values[..., 0] = 1.0
         tabulated = self.delay_doppler_model == "halimi14"
@@ -289,7 +268,7 @@ class NadirSARAltimetry(NadirLRMAltimetry):
                 incoherent = float(IterativeFirstOrder._dense(obj.diffuse_reflection_matrix(*args, mu, mu, np.pi, 2), 1)[0, 0, 0]) / e1.real
             below = complex(obj.permittivity(f)) if substrate else e2
             specular = float(np.asarray(reflection_diagonal(e1, below, mu, 2), float)[0, 0])
-            coherent = specular * float(np.exp(-4 * (wavenumber * obj.roughness_rms) ** 2 - (1 - mu[0] ** 2) / beta12) / beta12 / (4 * np.pi))
+            coherent = specular * float(coherent_factor(sensor0, wavenumber, obj.roughness_rms, mu[0]))
             if tabulated:   # one map for the volume and every boundary: no mean square slope enters
                 return coherent, incoherent, 0.0
             if incoherent > 0 and getattr(obj, "mean_square_slope", None) is None:
@@ -345,15 +324,23 @@ class _Solution(_LrmSolution):
     def _names(self, n_boundaries):
         return self.solver.contributions(n_boundaries)[0]
 
-    def _coords(self, sensor, n_boundaries=1):
+    def _coords(self, sensor, n_boundaries):
         coords = [("delay", self._delay(sensor)), ("doppler_frequency", self._doppler(sensor)), ("theta_inc", [0]), ("theta", [0])]
         names = self._names(n_boundaries)
         return ([("contribution", names)] if names else []) + coords
 
-    def _values(self, values, n_rows=None):
+    def _values(self, values, n_boundaries):
         """[..., rows, n_t, n_d] -> [..., n_t, n_d, 1, 1], or [..., n_rows, n_t, n_d, 1, 1] (the total is the last row)."""
+        n_rows = len(self._names(n_boundaries))
         values = values[..., :n_rows, :, :] if self.solver.return_contributions != "no" else values[..., 0, :, :]
         return values[..., None, None]
+
+    def _n_boundaries(self, out, slot):
+        return out.n_boundaries[slot]
+
+    def _stackable(self, n_boundaries):
+        """One contribution per interface: snowpacks of different depths do not share the coordinate."""
+        return self.solver.return_contributions != "full" or len(set(n_boundaries.tolist())) == 1
 
     @staticmethod
     def _attrs(sensor):
@@ -364,76 +351,6 @@ class _Solution(_LrmSolution):
         """z_gate lies on the delay of the data; the reference counts its delay from the first gate."""
         return ("delay", self._delay(sensor) + (sensor.nominal_gate / sensor.pulse_bandwidth if foreign else 0.0))
 
-    def result(self, i):
-        sensor, sp = self.sensors[self.sens_idx[i]], self.packs[self.pack_idx[i]]
-        out, row = self.outputs[self.group_of[i]], self.row_of[i]
-        u_packs, nl_solved, _, nb_solved = self.columns[self.group_of[i]]
-        slot = np.searchsorted(u_packs, self.pack_idx[i])
-        L, nb = int(nl_solved[slot]), int(nb_solved[slot])   # (after pruning)
-        lay = out.layers[row][:L]
-        layer_idx = ("layer", np.arange(L))
-        other = {
-            "effective_permittivity": LabeledArray(lay[:, 0] + 1j * lay[:, 1], [layer_idx]),
-            "ks": LabeledArray(lay[:, 2].copy(), [layer_idx], name="ks"),
-            "ke": LabeledArray(lay[:, 2] + lay[:, 3], [layer_idx], name="ke"),
-            "ka": LabeledArray(lay[:, 3].copy(), [layer_idx], name="ka"),
-            "backward_scattering": LabeledArray(lay[:, 4].copy(), [layer_idx], name="backward_scattering"),
-            "thickness": LabeledArray(np.asarray(sp.layer_thicknesses, float)[:L], [layer_idx], name="thickness"),
-        }
-        coords = self._coords(sensor, nb)
-        values = self._values(out.values[row], len(self._names(nb)))
-        foreign = self._foreign(sensor)
-        if foreign is not None:   # as the reference builds it: gate and doppler_bin as coordinates where xarray can
-            cls, labelled = foreign
-            data = labelled(values, coords)
-            if hasattr(data, "assign_coords"):
-                data = data.assign_coords(
-                    gate=("delay", self._delay(sensor) * sensor.pulse_bandwidth + sensor.nominal_gate),
+    def _foreign_coords(self, sensor):
+        return dict(_LrmSolution._foreign_coords(self, sensor),
                     doppler_bin=("doppler_frequency", self._doppler(sensor) / sensor.pulse_repetition_frequency * sensor.ndoppler))
-            res = cls(data, channel_map=sensor.channel_map,
-                      other_data={k: labelled(v.values, list(v.coords.items()), name=v.name) for k, v in other.items()})
-            res.z_gate = labelled(out.z_gate[row].copy(), [self._z_coord(sensor, foreign=True)], name="z_gate")
-            return res
-        z_gate = LabeledArray(out.z_gate[row].copy(), [self._z_coord(sensor)], name="z_gate")
-        return self._result(sensor, LabeledArray(values, coords), z_gate, other)
-
-    def stacked_result(self, plan):
-        if len(self.outputs) != 1 or not plan.dimensions:
-            return None
-        sensor0 = self.sensors[0]
-        if any(s.channel_map != sensor0.channel_map for s in self.sensors[1:]) or self._foreign(sensor0) is not None:
-            return None
-        out, order = self.outputs[0], self.row_of
-        u_packs, nl_solved, thick_solved, nb_solved = self.columns[0]
-        slot = np.full(len(self.packs), -1, np.int64)
-        slot[u_packs] = np.arange(len(u_packs))
-        nl = nl_solved[slot[self.pack_idx]]
-        nbs = nb_solved[slot[self.pack_idx]]
-        if self.solver.return_contributions == "full" and len(set(nbs.tolist())) != 1:
-            return None   # (one contribution per interface: snowpacks of different depths do not share the coordinate)
-        lead = [(name, np.asarray(list(values))) for name, values in plan.dimensions]
-        shape = tuple(len(v) for _, v in lead)
-        if int(np.prod(shape)) != len(order):
-            return None
-        nb = int(nbs[0])
-        values = self._values(out.values[order], len(self._names(nb)))
-        coords = self._coords(sensor0, nb)
-        data = LabeledArray(values.reshape(shape + values.shape[1:]), lead + coords)
-        z_gate = LabeledArray(out.z_gate[order].reshape(shape + (-1,)), lead + [self._z_coord(sensor0)], name="z_gate")
-        Lmax = int(nl.max())
-        lay = out.layers[order][:, :Lmax].copy()
-        below = np.arange(Lmax)[None, :] >= nl[:, None]
-        lay[below] = np.nan
-        thick = thick_solved.reshape(len(u_packs), -1)[slot[self.pack_idx], :Lmax].copy()
-        thick[below] = np.nan
-        layer_dim = [("layer", np.arange(Lmax))]
-
-        def stack(v, name=None):
-            return LabeledArray(v.reshape(shape + (Lmax,)), lead + layer_dim, name=name)
-
-        other = {
-            "effective_permittivity": stack(lay[:, :, 0] + 1j * lay[:, :, 1]),
-            "ks": stack(lay[:, :, 2], "ks"), "ke": stack(lay[:, :, 2] + lay[:, :, 3], "ke"), "ka": stack(lay[:, :, 3], "ka"),
-            "backward_scattering": stack(lay[:, :, 4], "backward_scattering"), "thickness": stack(thick, "thickness"),
-        }
-        return self._result(sensor0, data, z_gate, other)

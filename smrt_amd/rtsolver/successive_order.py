@@ -28,14 +28,14 @@ layers and kinds is DORT's (rtsolver/dort.py).  A whole Model.run is one launch 
 """
 import numpy as np
 
-from .._native import STATUS_MESSAGES
 from ..core.error import SMRTError
 from ..core.snowpack import Snowpack, substrate_kind
 from ..substrate.transparent import Transparent
-from .dort import DORT, _Solution as _DortSolution, get_context
+from .dort import _Solution as _DortSolution, get_context
+from .solver_base import RefusingPacker, SolverBase, check_error_handling
 
 
-class SuccessiveOrder(object):
+class SuccessiveOrder(SolverBase):
     """Options as smrt/rtsolver/successive_order.py; `devices` (list of GPU indices; the first is used) and
     `workspace_budget` (bytes the solver may reserve on the device; None: the library's default of 8 GiB) are smrt_amd's own
     knobs."""
@@ -52,8 +52,7 @@ class SuccessiveOrder(object):
                             "that it may not work)")
         if process_coherent_layers:
             raise SMRTError("process_coherent_layers is not available in the successive_order solver")
-        if error_handling not in ("exception", "nan"):
-            raise SMRTError("error_handling must be 'exception' or 'nan'")
+        check_error_handling(error_handling)
         if incident_polarizations not in ("V", "VH", "VHU"):
             raise SMRTError("The argument incident_polarizations must be V, VH or VHU. Note that H only is not supported yet.")
         if not 2 <= int(n_max_stream) <= 64:
@@ -76,62 +75,7 @@ class SuccessiveOrder(object):
         self.rayleigh_jeans_approximation = bool(rayleigh_jeans_approximation)
         self.devices = devices
         self.workspace_budget = workspace_budget
-        self.launches = 0      # launches of the last solve: tests assert "one launch per group"
-        self.launch_info = []  # per launch: dict(chunks, reserved_bytes, over_budget, budget)
-
-    # ---- the reference's protocol --------------------------------------------------------------------------------
-    def solve(self, snowpack, emmodels, sensor, atmosphere=None, parallel_computation=None):
-        from ..core.foreign import adopt_snowpack, entry_of_instance
-
-        self._check_sensor(sensor)
-        snowpack = adopt_snowpack(snowpack)
-        if atmosphere is not None or snowpack.atmosphere is not None:
-            raise SMRTError("the successive_order solver can not handle atmosphere yet.")
-        if len(emmodels) != snowpack.nlayer:
-            raise SMRTError("one emmodel per layer is needed")
-        entries = [entry_of_instance(e, layer) for e, layer in zip(emmodels, snowpack.layers)]
-        return self.solve_batch([(sensor, snowpack)], [entries])[0]
-
-    def solve_batch(self, simulations, emmodel):
-        """simulations: sequence of (single-frequency sensor, snowpack); one Result each (see DORT.solve_batch)."""
-        from ..core.foreign import adopt_snowpack
-
-        sensors, packs, si, pi = [], [], [], []
-        seen_s, seen_p, memo = {}, {}, {}
-        for sensor, sp in simulations:
-            sp = adopt_snowpack(sp, memo)
-            si.append(seen_s.setdefault(id(sensor), len(sensors)))
-            if si[-1] == len(sensors):
-                sensors.append(sensor)
-            pi.append(seen_p.setdefault(id(sp), len(packs)))
-            if pi[-1] == len(packs):
-                packs.append(sp)
-        if not si:
-            return []
-        names = emmodel if isinstance(emmodel, (list, str)) else DORT._device_name(emmodel)
-        sol = self._solve_indexed(sensors, packs, np.asarray(si), np.asarray(pi), names)
-        return [sol.result(i) for i in range(len(si))]
-
-    def solve_plan(self, model, plan):
-        """The whole plan of a Model.run, packed once and launched once per homogeneous group."""
-        from ..core.model import nest_results
-
-        for sensor in plan.sensors:
-            self._check_sensor(sensor)
-        packer = self._packer()
-        packer._plan_facts = {id(sp): sp.layer_facts() for sp in plan.snowpacks}
-        packer._plan_model = model
-        try:
-            names = DORT.emmodel_names(model, plan, packer._plan_facts)
-            sol = self._solve_indexed(plan.sensors, plan.snowpacks, plan.sensor_index, plan.snowpack_index, names, packer)
-        finally:
-            packer._plan_facts = packer._plan_model = None
-        stacked = sol.stacked_result(plan)
-        if stacked is not None:
-            return stacked
-        return nest_results([sol.result(i) for i in range(len(plan))], plan.dimensions)
-
-    emmodel_names = DORT.emmodel_names
+        self.launch_info = []
 
     # ---- grouping, packing, launching ----------------------------------------------------------------------------
     @staticmethod
@@ -144,7 +88,8 @@ class SuccessiveOrder(object):
                             "(Model.run does)")
 
     # what the active sibling (rtsolver/successive_order_backscatter.py) replaces; the grouping and the pair map are shared
-    _NAME = "successive_order"
+    NAME = "successive_order"
+    ATMOSPHERE = "the successive_order solver can not handle atmosphere yet."   # (solve: the active sibling says it in these words too)
 
     @staticmethod
     def _sensor_key(sensor):
@@ -152,17 +97,16 @@ class SuccessiveOrder(object):
         return tuple(np.round(sensor.theta_deg, 12))
 
     def _context(self):
-        return get_context((self.devices or [None])[0])
+        return get_context((self.devices or [None])[0])   # (this module's name: the CPU tests put a stand-in here)
 
-    @staticmethod
-    def _solution_class():
-        return _Solution
+    def _solution(self, sensors, packs, sens_idx, pack_idx):
+        return _Solution(self, sensors, packs, sens_idx, pack_idx)
 
-    def _run(self, ctx, batch, sensor0, pairs):
-        """One launch (under the context lock): its output and its launch_info."""
-        out = ctx.successive_order_run(batch, self.n_iteration_max, self.relative_tolerance, pairs=pairs,
+    def _launch(self, ctx, g):
+        out = ctx.successive_order_run(g.batch, self.n_iteration_max, self.relative_tolerance, pairs=g.pairs,
                                        workspace_budget=self.workspace_budget)
-        return out, ctx.successive_order_launch_info()
+        self.launch_info.append(ctx.successive_order_launch_info())
+        return out
 
     def _packer(self):
         return _Packer(n_max_stream=self.n_max_stream, m_max=self.m_max, error_handling=self.error_handling,
@@ -182,66 +126,21 @@ class SuccessiveOrder(object):
                             f"{type(sp.substrate).__name__} is not implemented.")
         return sp
 
-    def _solve_indexed(self, sensors, packs, sens_idx, pack_idx, emmodel_names, packer=None):
-        packer = packer or self._packer()
-        sensor_keys, pack_keys = {}, {}
-        s_code = np.empty(len(sensors), np.int64)
-        for k, sensor in enumerate(sensors):
-            self._check_sensor(sensor)
-            s_code[k] = sensor_keys.setdefault(self._sensor_key(sensor), len(sensor_keys))
-        p_code = np.empty(len(packs), np.int64)
-        packed = []
-        for k, sp in enumerate(packs):
-            if not isinstance(emmodel_names, str) and any(not isinstance(e, str) for e in emmodel_names[k]):
-                raise SMRTError(f"the {self._NAME} solver has no route for emmodels evaluated on the host: use an emmodel "
-                                "with a device implementation (iba, dmrt_qca_shortrange, dmrt_qcacp_shortrange, nonscattering)")
-            packed.append(self._check_snowpack(sp))
-            if packed[-1] is not sp and packer._plan_facts is not None:
-                packer._plan_facts[id(packed[-1])] = packer._plan_facts.get(id(sp))
-            p_code[k] = pack_keys.setdefault(substrate_kind(packed[-1].substrate), len(pack_keys))
-        freq = np.array([float(s.frequency) for s in sensors])
-        code = s_code[sens_idx] * len(pack_keys) + p_code[pack_idx]
-        sol = self._solution_class()(self, sensors, packs, sens_idx, pack_idx)
-        ctx = self._context()
-        self.launches, self.launch_info = 0, []
-        for g in np.unique(code):
-            sel = np.nonzero(code == g)[0]
-            u_packs, inv_p = np.unique(pack_idx[sel], return_inverse=True)
-            u_freq, inv_f = np.unique(freq[sens_idx[sel]], return_inverse=True)
-            sensor0 = sensors[sens_idx[sel[0]]]
-            sps = [packed[k] for k in u_packs]
-            names = emmodel_names if isinstance(emmodel_names, str) else [emmodel_names[k] for k in u_packs]
-            sensor_of = {float(sensors[k].frequency): sensors[k] for k in sens_idx[sel]}
-            batch = packer._pack(sensor0, sps, u_freq, names, sensor_of)
-            pairs = inv_f * len(u_packs) + inv_p
-            full = len(pairs) == batch.n_pairs and np.array_equal(pairs, np.arange(batch.n_pairs))
-            with ctx.lock:
-                out, info = self._run(ctx, batch, sensor0, None if full else pairs)
-                self.launch_info.append(info)
-            self.launches += 1
-            bad = np.nonzero(out.status != 0)[0]
-            if len(bad) and self.error_handling == "exception":
-                st = int(out.status[bad[0]])
-                message = STATUS_MESSAGES.get(st, f"the {self._NAME} solver failed with status {st}")
-                raise SMRTError(message.replace("N sublayers", f"{int(out.sublayers[bad[0]].sum())} sublayers"))
-            sol.add_group(sel, out, sps[0], (u_packs, np.array(batch.n_layers, np.int64), np.array(batch.thickness, float)))
-        return sol
+    def _snowpack_key(self, sp, on_host):
+        if on_host:
+            raise SMRTError(f"the {self.NAME} solver has no route for emmodels evaluated on the host: use an emmodel "
+                            "with a device implementation (iba, dmrt_qca_shortrange, dmrt_qcacp_shortrange, nonscattering)")
+        sp = self._check_snowpack(sp)
+        return sp, substrate_kind(sp.substrate)
+
+    def _status_message(self, out, at, status):
+        return SolverBase._status_message(self, out, at, status).replace("N sublayers", f"{int(out.sublayers[at].sum())} sublayers")
 
 
-class _Packer(DORT):
-    """DORT's packing of layers and kinds for this solver; everything DORT would evaluate on the host is refused."""
-
-    def _substrates_on_host(self, *args, **kwargs):
-        raise SMRTError("the successive_order solver takes no substrate, a Flat, a Reflector or a transparent one.")
-
-    def _interfaces_on_host(self, *args, **kwargs):
-        raise SMRTError("the successive_order solver takes Flat interfaces only: rough interfaces are not implemented.")
-
-    def _iba_scalars_on_host(self, *args, **kwargs):
-        raise SMRTError("the successive_order solver has no route for emmodels evaluated on the host.")
-
-    def _evaluate_on_host(self, *args, **kwargs):
-        raise SMRTError("the successive_order solver has no route for emmodels evaluated on the host.")
+class _Packer(RefusingPacker):
+    SUBSTRATES_ON_HOST = "the successive_order solver takes no substrate, a Flat, a Reflector or a transparent one."
+    INTERFACES_ON_HOST = "the successive_order solver takes Flat interfaces only: rough interfaces are not implemented."
+    IBA_SCALARS_ON_HOST = EVALUATE_ON_HOST = "the successive_order solver has no route for emmodels evaluated on the host."
 
 
 class _Solution(_DortSolution):

@@ -68,8 +68,8 @@ class SuccessiveOrderBackscatter(_PassiveSuccessiveOrder):
                             f"{type(sp.substrate).__name__} is not implemented.")
         return sp
 
-    # ---- the hooks of the passive solver's _solve_indexed (grouping, packing and the pair map are its) ------------------
-    _NAME = "successive_order_backscatter"
+    # ---- the other hooks the passive solver's differ in (grouping, packing and the pair map are shared) ------------------
+    NAME = "successive_order_backscatter"
 
     @staticmethod
     def _sensor_key(sensor):
@@ -78,15 +78,15 @@ class SuccessiveOrderBackscatter(_PassiveSuccessiveOrder):
     def _context(self):
         return get_context((self.devices or [None])[0])   # (this module's name: the CPU tests put a stand-in here)
 
-    @staticmethod
-    def _solution_class():
-        return _Solution
+    def _solution(self, sensors, packs, sens_idx, pack_idx):
+        return _Solution(self, sensors, packs, sens_idx, pack_idx)
 
-    def _run(self, ctx, batch, sensor0, pairs):
-        out = ctx.so_active_run(batch, np.atleast_1d(sensor0.theta_inc), self.n_iteration_max, self.relative_tolerance,
-                                incident_npol=len(self.incident_polarizations), m_max=self.m_max, pairs=pairs,
+    def _launch(self, ctx, g):
+        out = ctx.so_active_run(g.batch, np.atleast_1d(g.sensor0.theta_inc), self.n_iteration_max, self.relative_tolerance,
+                                incident_npol=len(self.incident_polarizations), m_max=self.m_max, pairs=g.pairs,
                                 workspace_budget=self.workspace_budget)
-        return out, ctx.so_active_launch_info()
+        self.launch_info.append(ctx.so_active_launch_info())
+        return out
 
 
 class _Solution(_PassiveSolution):
