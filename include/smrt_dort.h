@@ -88,6 +88,12 @@ typedef struct smrt_dort_ctx smrt_dort_ctx;
 #define SMRT_SUBSTRATE_FLAT 1       /* Fresnel against a given permittivity (substrate/flat.py) */
 #define SMRT_SUBSTRATE_REFLECTOR 2  /* prescribed specular reflection, emissivity 1 - R (substrate/reflector.py), passive only */
 #define SMRT_SUBSTRATE_HOST 3       /* rough substrate: dense reflection matrices (+ emissivity in passive mode) evaluated by the caller */
+/* Rough soils, passive mode only: Fresnel against the soil permittivity times a roughness factor per polarisation, evaluated
+ * per stream on the device; emissivity 1 - R.  Their parameters follow the permittivities in substrate_p1 / substrate_p2. */
+#define SMRT_SUBSTRATE_SOIL_WEGMULLER 4   /* Wegmuller & Maetzler 1999 (substrate/soil_wegmuller.py): roughness_rms */
+#define SMRT_SUBSTRATE_SOIL_QNH 5         /* Wang 1983 (substrate/soil_qnh.py): H, Q, Nv, Nh */
+#define SMRT_SUBSTRATE_ROUGH_CHOUDHURY 6  /* Choudhury et al. 1979 (substrate/rough_choudhury79.py): roughness_rms; a pair with
+                                           * ksigma > 0.1 in its last layer gets the status SMRT_ERR_INPUT */
 
 /* per-pair status word */
 #define SMRT_OK 0
@@ -127,8 +133,12 @@ typedef struct smrt_batch {
     double phi;               /* active: azimuth (rad), pi for backscatter (sensor.py:179-180) */
     /* substrate (smrt/substrate/flat.py, reflector.py; rtsolver_utils.py:544-605, dort.py:429-441), per pair because
      * permittivity / reflection models may depend on the frequency.  Unused (may be NULL) for SMRT_SUBSTRATE_NONE. */
-    const double* substrate_p1;          /* [F][S] flat: Re eps_substrate | reflector: specular reflection, V */
-    const double* substrate_p2;          /* [F][S] flat: Im eps_substrate | reflector: specular reflection, H */
+    const double* substrate_p1;          /* [F][S] flat: Re eps_substrate | reflector: specular reflection, V
+                                          * SMRT_SUBSTRATE_SOIL_WEGMULLER .. _ROUGH_CHOUDHURY: [F][S] Re eps_soil, FOLLOWED BY [S][2]:
+                                          * (roughness_rms in m, unused) for Wegmuller and Choudhury, (H, Q) for QNH */
+    const double* substrate_p2;          /* [F][S] flat: Im eps_substrate | reflector: specular reflection, H
+                                          * the soil kinds: [F][S] Im eps_soil, FOLLOWED BY [S][2]: (Nv, Nh) for QNH, unused
+                                          * (but present) for the two others */
     const double* substrate_temperature; /* [S] K; <= 0: the substrate does not emit (temperature=None) */
     /* SimpleIsotropicAtmosphere (smrt/atmosphere/simple_isotropic_atmosphere.py; rtsolver_utils.py:251-260,302-305),
      * passive mode only; all three NULL = no atmosphere */

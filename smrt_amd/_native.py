@@ -24,7 +24,8 @@ MS_CODES = {"exponential": 0, "sticky_hard_spheres": 1, "independent_sphere": 2,
             "unified_scaled_exponential": 0, "unified_sticky_hard_spheres": 1, "unified_teubner_strey": 3,
             "exponential_complex_k": 4, "sticky_hard_spheres_complex_k": 5, "independent_sphere_complex_k": 6,
             "teubner_strey_complex_k": 7}   # SMRT_MS_*_COMPLEX_K: layers of the strong-contrast-expansion emmodels
-SUBSTRATE_CODES = {"flat": 1, "reflector": 2, "host": 3}
+SUBSTRATE_CODES = {"flat": 1, "reflector": 2, "host": 3, "soil_wegmuller": 4, "soil_qnh": 5, "rough_choudhury79": 6}
+SOIL_KINDS = ("soil_wegmuller", "soil_qnh", "rough_choudhury79")   # SMRT_SUBSTRATE_SOIL_WEGMULLER .. _ROUGH_CHOUDHURY
 NORM_CODES = {False: 0, None: 0, True: 1, "auto": 1, "forced": 2}
 STATUS_MESSAGES = {
     1: "The eigen-decomposition did not converge in DORT.",
@@ -40,6 +41,16 @@ STATUS_MESSAGES = {
     8: "The multi-Fresnel chain gave a non-finite brightness temperature (a reflectivity of 1, e.g. at a grazing angle, divides "
        "by zero).",
 }
+# status 5 of a pair on a Choudhury substrate whose layer inputs are sound: the device has no other reason left
+CHOUDHURY_OUT_OF_RANGE = ("Invalid input (status 5): the Choudhury reflectivity is outside its validity range, ksigma must be "
+                          "<= 0.1 (ksigma << 1) -- or invalid layer properties")
+
+
+def status_message(batch, status, default=None):
+    """The text of a pair's status word; status 5 of a batch on a Choudhury substrate names the model's validity range."""
+    if status == 5 and int(batch.struct.substrate_kind) == SUBSTRATE_CODES["rough_choudhury79"]:
+        return CHOUDHURY_OUT_OF_RANGE
+    return default if default is not None else STATUS_MESSAGES.get(status)
 
 
 class SmrtBatch(C.Structure):
@@ -104,7 +115,10 @@ class PackedBatch:
                  prune_deep_snowpack=None, layer_kind=None, host_emmodel=None, process_coherent_layers=False,
                  host_interfaces=None, liquid_water=None, host_scalars=None):
         """substrate: None or (kind, p1[F][S], p2[F][S], temperature[S]) with kind "flat" (p1 + i p2 = permittivity) or
-        "reflector" (p1, p2 = specular reflection V, H); temperature <= 0 or NaN = no emission.
+        "reflector" (p1, p2 = specular reflection V, H); temperature <= 0 or NaN = no emission.  For the kinds
+        "soil_wegmuller", "soil_qnh", "rough_choudhury79" (passive mode) two more elements, tail1[S][2] and tail2[S][2]: p1 + i p2
+        is the soil permittivity, and the arrays handed to the library are p1 followed by tail1 (roughness_rms, 0 | H, Q) and
+        p2 followed by tail2 (0, 0 | Nv, Nh) (include/smrt_dort.h).
         atmosphere: None or (tb_down[F], tb_up[F], transmittance[F]).
         prune_deep_snowpack: None / False, True (= 6, smrt/rtsolver/dort.py:176-177) or the optical depth itself.
         layer_kind: None, or [S][Lmax] integer codes EM_CODES[emmodel] + 16 * MS_CODES[microstructure] for snowpacks
@@ -165,13 +179,25 @@ class PackedBatch:
                 self.sub_T = np.ascontiguousarray(np.nan_to_num(np.broadcast_to(np.asarray(substrate[3], np.float64), (S,)), nan=0.0))
                 s.substrate_temperature = _dptr(self.sub_T)
         elif substrate is not None:
-            kind, q1, q2, ts = substrate
+            kind, q1, q2, ts = substrate[:4]
             F = len(self.frequency)
             self.sub_p1 = np.ascontiguousarray(np.broadcast_to(np.asarray(q1, np.float64), (F, S)))
             self.sub_p2 = np.ascontiguousarray(np.broadcast_to(np.asarray(q2, np.float64), (F, S)))
+            if kind in SOIL_KINDS:
+                if len(substrate) != 6:
+                    raise SMRTError(f"a '{kind}' substrate needs its two parameter tails, [n_snowpacks][2] each")
+                if mode != "P":
+                    raise SMRTError(f"the '{kind}' substrate is evaluated on the device in passive mode only")
+                tails = [np.broadcast_to(np.asarray(t, np.float64), (S, 2)).reshape(-1) for t in substrate[4:]]
+                # one array each: [F][S] permittivities, then [S][2] parameters (sub_p1 / sub_p2 stay views of the front)
+                self.sub_p1_full = np.ascontiguousarray(np.concatenate([self.sub_p1.reshape(-1), tails[0]]))
+                self.sub_p2_full = np.ascontiguousarray(np.concatenate([self.sub_p2.reshape(-1), tails[1]]))
+                self.sub_p1, self.sub_p2 = self.sub_p1_full[:F * S].reshape(F, S), self.sub_p2_full[:F * S].reshape(F, S)
             self.sub_T = np.ascontiguousarray(np.nan_to_num(np.broadcast_to(np.asarray(ts, np.float64), (S,)), nan=0.0))
             s.substrate_kind = SUBSTRATE_CODES[kind]
             s.substrate_p1, s.substrate_p2, s.substrate_temperature = _dptr(self.sub_p1), _dptr(self.sub_p2), _dptr(self.sub_T)
+            if kind in SOIL_KINDS:
+                s.substrate_p1, s.substrate_p2 = _dptr(self.sub_p1_full), _dptr(self.sub_p2_full)
         if atmosphere is not None:
             F = len(self.frequency)
             self.atm = [np.ascontiguousarray(np.broadcast_to(np.asarray(a, np.float64), (F,))) for a in atmosphere]

@@ -173,6 +173,17 @@ def adopt_substrate(substrate):
             from ..substrate.reflector import Reflector
 
             return Reflector(temperature=substrate.temperature, specular_reflection=refl)
+    # the rough soils the device evaluates per stream in passive mode (in active mode smrt_amd's classes speak the substrate
+    # protocol themselves); the permittivity stays the reference's own substrate.permittivity(frequency), per pair
+    soils = (("soil_wegmuller", "SoilWegmuller", ("roughness_rms",)), ("soil_qnh", "SoilQNH", ("H", "Q", "N", "Nv", "Nh")),
+             ("rough_choudhury79", "ChoudhuryReflectivity", ("roughness_rms",)))
+    for module, name, parameters in soils:
+        if _is_exactly(cls, "substrate", module, name):
+            from .plugin import import_class
+
+            return import_class("substrate", "smrt_amd.substrate." + module)(
+                temperature=substrate.temperature, permittivity_model=lambda frequency, _t=None: substrate.permittivity(frequency),
+                **{p: getattr(substrate, p) for p in parameters})
     return substrate
 
 

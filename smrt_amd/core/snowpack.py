@@ -7,13 +7,16 @@ from .error import SMRTError
 from .layer import WRITES as LAYER_WRITES
 
 
-def substrate_kind(substrate):
-    """"flat" / "reflector" for the substrates the device evaluates itself, "host" for any other object that speaks the
-    reference's substrate protocol (smrt/core/interface.py:169-240: evaluated in Python, handed to the device as dense
-    reflection matrices, active mode), None for anything else."""
+def substrate_kind(substrate, mode="P"):
+    """"flat" / "reflector" / "soil_wegmuller" / "soil_qnh" / "rough_choudhury79" for the substrates the device evaluates
+    itself, "host" for any other object that speaks the reference's substrate protocol (smrt/core/interface.py:169-240:
+    evaluated in Python, handed to the device as dense reflection matrices), None for anything else.  The three soil models
+    are device kinds in passive mode only: for a sensor of mode "A" they are "host" objects."""
+    from .substrate import PASSIVE_DEVICE_KINDS
+
     kind = getattr(substrate, "device_kind", None)
-    if kind is None and callable(getattr(substrate, "specular_reflection_matrix", None)):
-        kind = "host"
+    if kind is None or (mode == "A" and kind in PASSIVE_DEVICE_KINDS):
+        kind = "host" if callable(getattr(substrate, "specular_reflection_matrix", None)) else None
     return kind
 
 

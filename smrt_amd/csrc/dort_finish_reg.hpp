@@ -528,9 +528,11 @@ enum { RT_SETUP = 0, RT_VEC, RT_AT, RT_APLUS, RT_HT, RT_INV, RT_ST1, RT_T2, RT_C
 // ------------------------------------------------------------------------------------------------------------
 // the per-pair driver: one wavefront (NT = 64)
 // ------------------------------------------------------------------------------------------------------------
-// Supported: passive mode, N <= 64, Flat interfaces, no / Flat / Reflector substrate, atmosphere, prune_deep_snowpack.
+// Supported: passive mode, N <= 64, Flat interfaces, no / Flat / Reflector substrate -- the SOIL instance: and the rough soils
+// (dort_physics.hpp: soil_RvRh) --, atmosphere, prune_deep_snowpack.
 // The host routes batches with process_coherent_layers (T != 1 - R) or a host-evaluated dense substrate to the two-slot
 // finish kernel (dort_hip.hip).
+template <bool SOIL = kSoilInstanceByDefault>
 SMRT_DEV void dort_pair_passive_reg(const DevBatch& b, long long p, double* lds_base, const DevStage& stg) {
     using namespace rg;
     constexpr int NT = 64, P = 2;
@@ -579,6 +581,8 @@ SMRT_DEV void dort_pair_passive_reg(const DevBatch& b, long long p, double* lds_
     {
         const int prev = b.status[p];
         if (prev != ST_OK) { fail_pair<NT>(b, p, prev, out_stride); return; }
+        // a substrate kind this instance has no code for (the host never launches it on one)
+        if (b.sub_kind > (SOIL ? SUB_ROUGH_CHOUDHURY : SUB_REFLECTOR) || b.sub_kind == SUB_HOST) { fail_pair<NT>(b, p, ST_INPUT, out_stride); return; }
     }
     {
         const int st = pair_setup<NT>(b, s, frequency, L, thickness, fracvol, temperature, mp1, mp2,
@@ -607,6 +611,8 @@ SMRT_DEV void dort_pair_passive_reg(const DevBatch& b, long long p, double* lds_
         const int bad = first_failed_layer(stg, p * (long long)b.Lmax, Lk);
         if (bad != ST_OK) { fail_pair<NT>(b, p, bad, out_stride); return; }
     }
+    // a Choudhury substrate out of its range under this pair's last layer (uniform; not where pruning hides the substrate)
+    if (SOIL && Lk == L && !substrate_in_range(b, si, frequency, cmk(s.eps_re[L - 1], s.eps_im[L - 1]))) { fail_pair<NT>(b, p, ST_INPUT, out_stride); return; }
 
     double n3 = 0.0;
     // element t of the vectors carried from layer to layer: source c of the relation (physical coordinates of the layer it
@@ -647,6 +653,11 @@ SMRT_DEV void dort_pair_passive_reg(const DevBatch& b, long long p, double* lds_
                 else if (b.sub_kind != SUB_NONE) {
                     const double q1 = b.sub_p1[gp], q2 = b.sub_p2[gp];
                     Rs = (b.sub_kind == SUB_FLAT) ? flat_R(el, cmk(q1, q2), rs, t & 1) : ((t & 1) ? q2 : q1);
+                    if (SOIL && b.sub_kind > SUB_REFLECTOR) {   // a rough soil: once per (pair, stream), like the Flat substrate
+                        double Rv, Rh;
+                        substrate_RvRh(b, gp, si, frequency, el, sqrt(1.0 - rs * rs), &Rv, &Rh);
+                        Rs = (t & 1) ? Rh : Rv;
+                    }
                     const double Ts = b.sub_T[si];
                     if (Ts > 0.0) src = (1.0 - Rs) * (b.rayleigh_jeans ? Ts : planck_radiance(frequency, Ts));
                 }

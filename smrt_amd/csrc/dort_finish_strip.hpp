@@ -366,10 +366,11 @@ static SMRT_DEV void strip_invert(Strip& M, int nt, int w, const Lane& L, double
 // ------------------------------------------------------------------------------------------------------------
 // the per-pair driver: one workgroup of NTT wavefronts
 // ------------------------------------------------------------------------------------------------------------
-// Supported: passive mode, N <= 16 NTT, Flat interfaces, no / Flat / Reflector substrate, atmosphere, prune_deep_snowpack.
+// Supported: passive mode, N <= 16 NTT, Flat interfaces, no / Flat / Reflector substrate -- the SOIL instance: and the rough soils
+// (dort_physics.hpp: soil_RvRh) --, atmosphere, prune_deep_snowpack.
 // The host routes batches with process_coherent_layers (T != 1 - R), a host-evaluated dense substrate or rough interfaces
 // to the pivoted finish kernels (dort_hip.hip).
-template <bool MAY_DIRECT>
+template <bool MAY_DIRECT, bool SOIL>
 static SMRT_DEV void run(const DevBatch& b, long long p, double* lds_base, const DevStage& stg) {
     constexpr int NT = NTH, P = 2;
     const LaneId Ln0 = rg::lane_id();
@@ -409,6 +410,8 @@ static SMRT_DEV void run(const DevBatch& b, long long p, double* lds_base, const
     {
         const int prev = b.status[p];
         if (prev != ST_OK) { fail_pair<NT>(b, p, prev, out_stride); return; }
+        // a substrate kind this instance has no code for (the host never launches it on one)
+        if (b.sub_kind > (SOIL ? SUB_ROUGH_CHOUDHURY : SUB_REFLECTOR) || b.sub_kind == SUB_HOST) { fail_pair<NT>(b, p, ST_INPUT, out_stride); return; }
     }
     {
         const int st = pair_setup<NT>(b, s, frequency, L, thickness, fracvol, temperature, mp1, mp2,
@@ -437,6 +440,8 @@ static SMRT_DEV void run(const DevBatch& b, long long p, double* lds_base, const
         const int bad = first_failed_layer(stg, p * (long long)b.Lmax, Lk);
         if (bad != ST_OK) { fail_pair<NT>(b, p, bad, out_stride); return; }
     }
+    // a Choudhury substrate out of its range under this pair's last layer (uniform; not where pruning hides the substrate)
+    if (SOIL && Lk == L && !substrate_in_range(b, si, frequency, cmk(s.eps_re[L - 1], s.eps_im[L - 1]))) { fail_pair<NT>(b, p, ST_INPUT, out_stride); return; }
     const int LD = (nmax * P + 1) | 1;   // leading dimension of the staged matrices (make_plan)
 
 #ifdef SMRT_STRIP_TIMING
@@ -554,6 +559,11 @@ static SMRT_DEV void run(const DevBatch& b, long long p, double* lds_base, const
                 else if (b.sub_kind != SUB_NONE) {
                     const double q1 = b.sub_p1[gp], q2 = b.sub_p2[gp];
                     Rs = (b.sub_kind == SUB_FLAT) ? flat_R(el, cmk(q1, q2), rs, t & 1) : ((t & 1) ? q2 : q1);
+                    if (SOIL && b.sub_kind > SUB_REFLECTOR) {   // a rough soil: once per (pair, stream), like the Flat substrate
+                        double Rv, Rh;
+                        substrate_RvRh(b, gp, si, frequency, el, sqrt(1.0 - rs * rs), &Rv, &Rh);
+                        Rs = (t & 1) ? Rh : Rv;
+                    }
                     const double Ts = b.sub_T[si];
                     if (Ts > 0.0) src = (1.0 - Rs) * (b.rayleigh_jeans ? Ts : planck_radiance(frequency, Ts));
                 }
@@ -885,13 +895,14 @@ static SMRT_DEV void run(const DevBatch& b, long long p, double* lds_base, const
 SMRT_HD int finish_strip_lds_doubles(int n_max_stream, int Lmax, int ntt = 8) {
     return ntt * ntt * 16 * 17 + 12 * 16 * ntt + 3 * n_max_stream + 15 * Lmax + 8;
 }
+template <bool SOIL = kSoilInstanceByDefault>
 SMRT_DEV void dort_pair_passive_strip(const DevBatch& b, long long p, double* lds_base, const DevStage& stg) {
-    StripFinish<8>::run<true>(b, p, lds_base, stg);
+    StripFinish<8>::run<true, SOIL>(b, p, lds_base, stg);
 }
 // MAY_DIRECT: the batch may hold layers the Rayleigh kernel diagonalised in closed form (DevBatch::rayleigh_direct)
-template <bool MAY_DIRECT>
+template <bool MAY_DIRECT, bool SOIL = kSoilInstanceByDefault>
 SMRT_DEV void dort_pair_passive_strip4(const DevBatch& b, long long p, double* lds_base, const DevStage& stg) {
-    StripFinish<4>::run<MAY_DIRECT>(b, p, lds_base, stg);
+    StripFinish<4>::run<MAY_DIRECT, SOIL>(b, p, lds_base, stg);
 }
 
 }  // namespace smrt

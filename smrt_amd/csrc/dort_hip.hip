@@ -532,8 +532,9 @@ static int32_t upload_impl(smrt_dort_ctx* ctx, const smrt_batch* b, int64_t pair
         if (b->substrate_temperature && upload_array(ctx, ctx->d_subT, b->substrate_temperature, sizeof(double) * b->n_snowpacks)) return -1;
     } else
     if (b->substrate_kind != SMRT_SUBSTRATE_NONE) {
-        if (upload_array(ctx, ctx->d_sub1, b->substrate_p1, sizeof(double) * FS)) return -1;
-        if (upload_array(ctx, ctx->d_sub2, b->substrate_p2, sizeof(double) * FS)) return -1;
+        const size_t sub_doubles = smrt_host::substrate_array_doubles(b);   // (the rough soils: + [S][2] parameters, smrt_dort.h)
+        if (upload_array(ctx, ctx->d_sub1, b->substrate_p1, sizeof(double) * sub_doubles)) return -1;
+        if (upload_array(ctx, ctx->d_sub2, b->substrate_p2, sizeof(double) * sub_doubles)) return -1;
         if (upload_array(ctx, ctx->d_subT, b->substrate_temperature, sizeof(double) * b->n_snowpacks)) return -1;
     }
     std::vector<double> atm;

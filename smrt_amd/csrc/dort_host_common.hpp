@@ -104,6 +104,14 @@ inline int out_stride(const smrt_batch* b) {
     return (b->mode == SMRT_MODE_PASSIVE) ? 2 * b->n_theta : 9 * b->n_theta;
 }
 
+// The rough soils the device evaluates per stream in passive mode: substrate_p1 / substrate_p2 carry [S][2] parameters behind
+// their [F][S] permittivities (smrt_dort.h).
+inline bool is_soil_substrate(int kind) { return kind >= SMRT_SUBSTRATE_SOIL_WEGMULLER && kind <= SMRT_SUBSTRATE_ROUGH_CHOUDHURY; }
+// doubles in substrate_p1 (and in substrate_p2) of a batch with a substrate of this kind
+inline size_t substrate_array_doubles(const smrt_batch* b) {
+    return (size_t)b->n_frequencies * b->n_snowpacks + (is_soil_substrate(b->substrate_kind) ? 2 * (size_t)b->n_snowpacks : 0);
+}
+
 inline const char* validate(const smrt_batch* b) {
     if (!b) return "null batch";
     if (b->n_snowpacks <= 0 || b->n_frequencies <= 0 || b->n_layers_max <= 0) return "empty batch";
@@ -144,7 +152,7 @@ inline const char* validate(const smrt_batch* b) {
         !b->theta)
         return "null input array";
     if ((b->microstructure == SMRT_MS_STICKY_HARD_SPHERES || b->layer_kind) && !b->micro_p2) return "stickiness array missing";
-    if (b->substrate_kind < SMRT_SUBSTRATE_NONE || b->substrate_kind > SMRT_SUBSTRATE_HOST) return "unknown substrate kind";
+    if (b->substrate_kind < SMRT_SUBSTRATE_NONE || b->substrate_kind > SMRT_SUBSTRATE_ROUGH_CHOUDHURY) return "unknown substrate kind";
     if (b->substrate_kind == SMRT_SUBSTRATE_HOST) {
         if (!b->host_substrate || !b->host_substrate_coh) return "SMRT_SUBSTRATE_HOST needs host_substrate and host_substrate_coh";
         if (b->mode == SMRT_MODE_PASSIVE && !b->substrate_temperature) return "SMRT_SUBSTRATE_HOST in passive mode needs substrate_temperature";
@@ -153,6 +161,8 @@ inline const char* validate(const smrt_batch* b) {
         return "substrate arrays missing";
     if (b->substrate_kind == SMRT_SUBSTRATE_REFLECTOR && b->mode == SMRT_MODE_ACTIVE)
         return "the reflector substrate has no third Stokes component: passive mode only (smrt/substrate/reflector.py)";
+    if (is_soil_substrate(b->substrate_kind) && b->mode == SMRT_MODE_ACTIVE)
+        return "the Wegmuller, QNH and Choudhury substrates are evaluated on the device in passive mode only: hand them over as SMRT_SUBSTRATE_HOST in active mode";
     if (b->host_interface_slot) {
         if (!b->host_interface || !b->host_interface_coh || b->host_interface_slots < 1)
             return "host_interface_slot needs host_interface, host_interface_coh and host_interface_slots >= 1";
@@ -176,6 +186,7 @@ struct SolverAccepts {
     int substrate_last;              // substrate kinds SMRT_SUBSTRATE_NONE .. substrate_last are taken ...
     const char* substrate_refusal;   // ... the others refused with this message
     bool substrate_temperature;      // a substrate needs substrate_temperature too
+    bool soil_substrates = false;    // SMRT_SUBSTRATE_SOIL_WEGMULLER .. _ROUGH_CHOUDHURY are taken as well (they always need all three arrays)
 };
 constexpr unsigned kHostEmmodels = 1u << SMRT_EM_HOST | 1u << SMRT_EM_IBA_HOST | 1u << SMRT_EM_RAYLEIGH_HOST;
 
@@ -217,8 +228,9 @@ inline const char* refuse_inputs(const smrt_batch* b, const SolverAccepts& a) {
 }
 
 inline const char* refuse_substrate(const smrt_batch* b, const SolverAccepts& a) {
-    if (b->substrate_kind < SMRT_SUBSTRATE_NONE || b->substrate_kind > a.substrate_last) return a.substrate_refusal;
-    if (b->substrate_kind != SMRT_SUBSTRATE_NONE && (!b->substrate_p1 || !b->substrate_p2 || (a.substrate_temperature && !b->substrate_temperature)))
+    const bool soil = is_soil_substrate(b->substrate_kind);
+    if (b->substrate_kind < SMRT_SUBSTRATE_NONE || (soil ? !a.soil_substrates : b->substrate_kind > a.substrate_last)) return a.substrate_refusal;
+    if (b->substrate_kind != SMRT_SUBSTRATE_NONE && (!b->substrate_p1 || !b->substrate_p2 || ((a.substrate_temperature || soil) && !b->substrate_temperature)))
         return "substrate arrays missing";
     return nullptr;
 }

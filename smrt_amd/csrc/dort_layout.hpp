@@ -50,7 +50,7 @@ struct DevBatch {
     const double* liquid_water;  // [S][Lmax] liquid water of wet layers (water / (ice + water) volume), or null: dry snow
     const double* gl_mu;  // [n_max_stream] positive Gauss-Legendre nodes of order 2 n_max, descending
     int sub_kind;                         // 0 none, 1 flat (p1 + i p2 = permittivity), 2 reflector (p1, p2 = R_V, R_H)
-    const double *sub_p1, *sub_p2;        // [F][S]
+    const double *sub_p1, *sub_p2;        // [F][S]; 4-6, the rough soils: the permittivity, then [S][2] parameters (soil_RvRh)
     const double* sub_T;                  // [S], <= 0: no emission
     const double *atm_down, *atm_up, *atm_trans;  // [F] or null
     double phi;
@@ -135,7 +135,17 @@ enum { EM_IBA = 0, EM_DMRT = 1, EM_QCACP = 2, EM_NONSCAT = 3, EM_HOST = 4, EM_IB
 SMRT_HD_EARLY bool em_has_rayleigh_phase(int em) { return em == EM_DMRT || em == EM_QCACP || em == EM_NONSCAT || em == EM_RAYLEIGH_HOST; }
 enum { MS_EXP = 0, MS_SHS = 1, MS_SPHERE = 2, MS_TS = 3, MS_EXPC = 4, MS_SHSC = 5, MS_SPHEREC = 6, MS_TSC = 7 };   // 4 + model: the model at a complex wavenumber (smrt_dort.h)
 enum { ST_OK = 0, ST_EIGEN = 1, ST_NORM = 2, ST_ALBEDO = 3, ST_SINGULAR = 4, ST_INPUT = 5, ST_COHERENT = 6 };
-enum { SUB_NONE = 0, SUB_FLAT = 1, SUB_REFLECTOR = 2, SUB_HOST = 3 };
+// The strip and register-resident finish kernels exist in two instances: SOIL = false, the headline kernels, with no code for
+// the rough soils (kinds above SUB_REFLECTOR fail the pair there), and SOIL = true, which evaluates them and is launched for
+// soil batches only (dort_hip.hip; DESIGN.md 4i: the soil code in the headline instance cost the batch without a substrate
+// scratch and time).  The entry points default to the instance the library launches for a batch without soil; under the CPU
+// emulator, whose entry points take any batch, to the one that evaluates everything.
+#if defined(SMRT_HOST_EMU)
+constexpr bool kSoilInstanceByDefault = true;
+#else
+constexpr bool kSoilInstanceByDefault = false;
+#endif
+enum { SUB_NONE = 0, SUB_FLAT = 1, SUB_REFLECTOR = 2, SUB_HOST = 3, SUB_SOIL_WEGMULLER = 4, SUB_SOIL_QNH = 5, SUB_ROUGH_CHOUDHURY = 6 };
 
 // ------------------------------------------------------------------------------------------------------------
 // LDS layout (shared by host sizing code and the kernel)

@@ -350,6 +350,9 @@ SMRT_DEV void dort_pair_passive(const DevBatch& b, long long p, double* lds_base
         if (t == 0) { stg->n[p * (long long)b.Lmax + l] = -code; s.ints[0] = ST_OK; }
         block_sync();
     };
+    // a Choudhury substrate out of its range under this pair's last layer (uniform): the reference raises -- not where
+    // prune_deep_snowpack cut the recursion above the substrate, which is then never evaluated
+    if (MODE != 1 && Lk == L && !substrate_in_range(b, si, frequency, cmk(s.eps_re[L - 1], s.eps_im[L - 1]))) { fail_pair<NT>(b, p, ST_INPUT, out_stride); return; }
     bool rough_surface = false;   // the surface is a rough interface: R~ (air side) and s are in M3 / svec after the loop
     // ---- bottom-up over the layers -------------------------------------------------------------------------
     if (MODE == 1 && b.pair_done && b.pair_done[p]) return;   // the cut of this pair lies above this round's layers (uniform)
@@ -398,6 +401,11 @@ SMRT_DEV void dort_pair_passive(const DevBatch& b, long long p, double* lds_base
                         const double rs = s.ri[l] * s.gsin[r >> 1];
                         double Rv, Rh;
                         fresnel_RvRh(el, cmk(q1, q2), sqrt(1.0 - rs * rs), &Rv, &Rh);
+                        Rs = (r & 1) ? Rh : Rv;
+                    } else if (b.sub_kind != SUB_REFLECTOR) {   // a rough soil: Fresnel and the model's adjustment
+                        const double rs = s.ri[l] * s.gsin[r >> 1];
+                        double Rv, Rh;
+                        substrate_RvRh(b, gpi, si, frequency, el, sqrt(1.0 - rs * rs), &Rv, &Rh);
                         Rs = (r & 1) ? Rh : Rv;
                     } else Rs = (r & 1) ? q2 : q1;
                     const double Ts = b.sub_T[si];

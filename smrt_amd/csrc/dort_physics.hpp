@@ -308,6 +308,69 @@ SMRT_DEV void fresnel_RvRh(cplx e1, cplx e2, double mu1, double* Rv, double* Rh)
     *Rh = cabs2(rh);
 }
 
+// The rough soils of the passive solvers (smrt/substrate/soil_wegmuller.py, soil_qnh.py, rough_choudhury79.py): Fresnel's power
+// reflection against the soil permittivity e2, seen from the last layer (e1, cosine mu1), then the model's adjustment of BOTH
+// polarisations (QNH mixes them).  The parameters follow the [F][S] permittivities in the substrate arrays (smrt_dort.h): a0, a1
+// from substrate_p1 and c0, c1 from substrate_p2 --
+//   SUB_SOIL_WEGMULLER   a0 = roughness_rms;  R_h e^(-ksigma^sqrt(0.1 mu)), R_v = R_h mu^0.655 up to 60 degrees, R_h (0.635 - 0.0014
+//                        (theta - 60)) beyond (the test is mu < cos(60 pi / 180), as the reference writes it)
+//   SUB_SOIL_QNH         a0 = H, a1 = Q, c0 = Nv, c1 = Nh;  ((1 - Q) R_v + Q R_h) e^(-H mu^Nv) and likewise for H with Nh
+//   SUB_ROUGH_CHOUDHURY  a0 = roughness_rms;  both times e^(-4 ksigma^2 mu^2); invalid where ksigma > 0.1
+// ksigma = Re(2 pi f sqrt(e1 / c^2)) roughness_rms with c = 2.9979e8 as both models of the reference write it -- NOT kCSpeed: the
+// 4e-6 between the two shows in a brightness temperature held to 1e-6 K.  Returns false where the model is out of its range.
+constexpr double kSoilCSpeed = 2.9979e8;
+constexpr double kChoudhuryKsigmaMax = 0.1;
+SMRT_DEV double soil_ksigma(double frequency, cplx e1, double roughness_rms) {
+    const double ic = 1.0 / kSoilCSpeed;
+    return 2.0 * kPi * frequency * csqrt_(cscale(e1, ic * ic)).re * roughness_rms;
+}
+SMRT_DEV bool soil_in_range(int kind, double frequency, cplx e1, double a0) {
+    return !(kind == SUB_ROUGH_CHOUDHURY && soil_ksigma(frequency, e1, a0) > kChoudhuryKsigmaMax);
+}
+// (not inlined: the transcendental functions of the models stay out of the register allocation of the kernels that call it once
+// per (pair, stream), in a cold branch.  The strip and register-resident finish kernels call it from an instance of their own
+// that is launched for soil batches only -- in the headline instance even the call cost the batch without a substrate scratch
+// and 0.5 % of its time: dort_layout.hpp kSoilInstanceByDefault)
+SMRT_DEV_NOINLINE bool soil_RvRh(int kind, double a0, double a1, double c0, double c1, double frequency, cplx e1, cplx e2, double mu1,
+                        double* Rv, double* Rh) {
+    double rv, rh;
+    fresnel_RvRh(e1, e2, mu1, &rv, &rh);
+    bool valid = true;
+    if (kind == SUB_SOIL_QNH) {
+        const double mv = ((1.0 - a1) * rv + a1 * rh) * exp(-a0 * pow(mu1, c0));
+        rh = ((1.0 - a1) * rh + a1 * rv) * exp(-a0 * pow(mu1, c1));
+        rv = mv;
+    } else {
+        const double ks = soil_ksigma(frequency, e1, a0);
+        if (kind == SUB_SOIL_WEGMULLER) {
+            rh *= exp(-pow(ks, sqrt(0.1 * mu1)));
+            rv = (mu1 < cos(60.0 * kPi / 180.0)) ? rh * (0.635 - 0.0014 * (acos(mu1) * 180.0 / kPi - 60.0)) : rh * pow(mu1, 0.655);
+        } else {
+            valid = !(ks > kChoudhuryKsigmaMax);
+            const double damping = exp(-4.0 * ks * ks * mu1 * mu1);
+            rv *= damping; rh *= damping;
+        }
+    }
+    *Rv = rv; *Rh = rh;
+    return valid;
+}
+
+// R_v, R_h of the bottom boundary of a passive batch whose substrate is Flat or a rough soil, for the pair gp = f * S + si, seen
+// from the last layer (el) under the cosine mu: what every passive kernel calls where it evaluates the substrate (DevBatch and
+// SoBatch name the fields alike).  False where the soil model is out of its range (the kernels fail such a pair beforehand).
+template <class Batch>
+SMRT_DEV bool substrate_RvRh(const Batch& b, long long gp, int si, double frequency, cplx el, double mu, double* Rv, double* Rh) {
+    const cplx es = cmk(b.sub_p1[gp], b.sub_p2[gp]);
+    if (b.sub_kind == SUB_FLAT) { fresnel_RvRh(el, es, mu, Rv, Rh); return true; }
+    const long long tail = (long long)b.F * b.S + 2 * si;
+    return soil_RvRh(b.sub_kind, b.sub_p1[tail], b.sub_p1[tail + 1], b.sub_p2[tail], b.sub_p2[tail + 1], frequency, el, es, mu, Rv, Rh);
+}
+// A pair on a Choudhury substrate whose ksigma in the last layer (el) exceeds the model's range: status ST_INPUT
+template <class Batch>
+SMRT_DEV bool substrate_in_range(const Batch& b, int si, double frequency, cplx el) {
+    return b.sub_kind != SUB_ROUGH_CHOUDHURY || soil_in_range(b.sub_kind, frequency, el, b.sub_p1[(long long)b.F * b.S + 2 * si]);
+}
+
 // DORT option process_coherent_layers (smrt/interface/coherent_flat.py:60-186): a layer thinner than 3/8 of a wavelength
 // and its two flat interfaces collapsed into ONE interface between medium 1 (incidence, cosine mu1) and medium 2.
 // Field reflection / transmission coefficients of the slab (Tsang I 5.2.10-14) and the cosine in medium 2.

@@ -11,14 +11,20 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(1, 1))) void
     extern __shared__ __attribute__((aligned(16))) double smrt_lds[];
     dort_pair_passive_reg(b, dispatched_pair(b, (long long)blockIdx.x), smrt_lds, st);
 }
+// ... and the instance that evaluates the rough soils, launched for batches on one of them only (dort_layout.hpp)
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(1, 1))) void dort_finish_reg_soil_kernel(DevBatch b, DevStage st) {
+    extern __shared__ __attribute__((aligned(16))) double smrt_lds[];
+    dort_pair_passive_reg<true>(b, dispatched_pair(b, (long long)blockIdx.x), smrt_lds, st);
+}
 
 namespace smrt_launch {
 
 hipError_t finish_reg(smrt_dort_ctx* ctx, const DevBatch& c) {
     const size_t lds = ctx->finish_reg_lds_bytes;
-    hipError_t e = hipFuncSetAttribute((const void*)dort_finish_reg_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    auto* const kernel = c.sub_kind > SUB_HOST ? dort_finish_reg_soil_kernel : dort_finish_reg_kernel;
+    hipError_t e = hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(dort_finish_reg_kernel, dim3((unsigned)c.pair_count), dim3(64), lds, ctx->stream, c, ctx->stage);
+    hipLaunchKernelGGL(kernel, dim3((unsigned)c.pair_count), dim3(64), lds, ctx->stream, c, ctx->stage);
     return hipGetLastError();
 }
 

@@ -16,6 +16,12 @@ __global__ __launch_bounds__(512, 2) void dort_finish_strip_kernel(DevBatch b, D
 }
 
 // the same recursion on four wavefronts for N <= 64 (LDS pipeline): 44 KB of LDS, three workgroups per CU, three wavefronts per SIMD
+// ... and the instances that evaluate the rough soils, launched for batches on one of them only (dort_layout.hpp)
+__global__ __launch_bounds__(512, 2) void dort_finish_strip_soil_kernel(DevBatch b, DevStage st) {
+    extern __shared__ __attribute__((aligned(16))) double smrt_lds[];
+    dort_pair_passive_strip<true>(b, dispatched_pair(b, (long long)blockIdx.x), smrt_lds, st);
+}
+
 #ifndef SMRT_STRIP4_WAVES
 #define SMRT_STRIP4_WAVES 3
 #endif
@@ -28,12 +34,17 @@ __global__ __launch_bounds__(256, SMRT_STRIP4_WAVES) void dort_finish_strip4_dir
     extern __shared__ __attribute__((aligned(16))) double smrt_lds[];
     dort_pair_passive_strip4<true>(b, dispatched_pair(b, (long long)blockIdx.x), smrt_lds, st);
 }
+__global__ __launch_bounds__(256, SMRT_STRIP4_WAVES) void dort_finish_strip4_soil_kernel(DevBatch b, DevStage st) {
+    extern __shared__ __attribute__((aligned(16))) double smrt_lds[];
+    dort_pair_passive_strip4<true, true>(b, dispatched_pair(b, (long long)blockIdx.x), smrt_lds, st);   // (with or without closed-form layers)
+}
 
 namespace smrt_launch {
 
 hipError_t finish_strip4(smrt_dort_ctx* ctx, const DevBatch& c) {
     const size_t lds = ctx->finish_strip4_lds_bytes;
-    auto* const kernel = c.rayleigh_direct ? dort_finish_strip4_direct_kernel : dort_finish_strip4_kernel;
+    auto* const kernel = c.sub_kind > SUB_HOST ? dort_finish_strip4_soil_kernel
+                         : c.rayleigh_direct ? dort_finish_strip4_direct_kernel : dort_finish_strip4_kernel;
     hipError_t e = hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL(kernel, dim3((unsigned)c.pair_count), dim3(256), lds, ctx->stream, c, ctx->stage);
@@ -42,9 +53,10 @@ hipError_t finish_strip4(smrt_dort_ctx* ctx, const DevBatch& c) {
 
 hipError_t finish_strip(smrt_dort_ctx* ctx, const DevBatch& c) {
     const size_t lds = ctx->finish_strip_lds_bytes;
-    hipError_t e = hipFuncSetAttribute((const void*)dort_finish_strip_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    auto* const kernel = c.sub_kind > SUB_HOST ? dort_finish_strip_soil_kernel : dort_finish_strip_kernel;
+    hipError_t e = hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(dort_finish_strip_kernel, dim3((unsigned)c.pair_count), dim3(512), lds, ctx->stream, c, ctx->stage);
+    hipLaunchKernelGGL(kernel, dim3((unsigned)c.pair_count), dim3(512), lds, ctx->stream, c, ctx->stage);
     return hipGetLastError();
 }
 

@@ -116,8 +116,10 @@ int upload_batch(smrt_dort_ctx* ctx, InputState* st, const smrt_batch* b, const 
     if (b->micro_p2 && upload(ctx, st->p2, b->micro_p2, SL, d.p2)) return -1;
     if (b->liquid_water && upload(ctx, st->lw, b->liquid_water, SL, d.liquid_water)) return -1;
     if (b->layer_kind && upload(ctx, st->kind, b->layer_kind, S * L * sizeof(int32_t), d.layer_kind)) return -1;
-    if (d.sub_kind != SMRT_SUBSTRATE_NONE && (upload(ctx, st->sub1, b->substrate_p1, F * S * sizeof(double), d.sub_p1) ||
-                                              upload(ctx, st->sub2, b->substrate_p2, F * S * sizeof(double), d.sub_p2)))
+    // (the rough soils: their [S][2] parameters follow the [F][S] permittivities in both arrays, smrt_dort.h)
+    const size_t sub_bytes = (F * S + (smrt_host::is_soil_substrate(d.sub_kind) ? 2 * S : 0)) * sizeof(double);
+    if (d.sub_kind != SMRT_SUBSTRATE_NONE && (upload(ctx, st->sub1, b->substrate_p1, sub_bytes, d.sub_p1) ||
+                                              upload(ctx, st->sub2, b->substrate_p2, sub_bytes, d.sub_p2)))
         return -1;
     if (pairs && upload(ctx, st->pairmap, pairs, (size_t)d.n_pairs * sizeof(int64_t), d.pair_map)) return -1;
     return 0;

@@ -61,7 +61,8 @@ inline const char* second_order(const smrt_batch* b) {
 
 inline const char* successive_order(const smrt_batch* b, int32_t n_iter, double rtol) {
     static const SolverAccepts accepts{true, true, kHostEmmodels, "the successive_order solver has no route for emmodels evaluated on the host", nullptr,
-                                       SMRT_SUBSTRATE_REFLECTOR, "the successive_order solver takes no substrate, a flat one or a reflector", false};
+                                       SMRT_SUBSTRATE_REFLECTOR, "the successive_order solver takes no substrate, a flat one or a reflector", false,
+                                       true};   // (and the rough soils, which are diagonal per stream like the flat one)
     const char* why = refuse_empty(b);
     if (why) return why;
     if (b->n_theta <= 0) return "n_theta must be positive";

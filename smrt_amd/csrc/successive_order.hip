@@ -77,7 +77,7 @@ int32_t smrt_successive_order_upload_pairs(smrt_dort_ctx* ctx, const smrt_batch*
     const size_t out_bytes[] = {(size_t)SO_ROWS * L * N * 8, N * L * 4, N * L * 4, N * L * SO_VECS * Dh * 8, N * L * 8, N * 8,
                                 N * (NO + 1) * 2 * T * 8, N * 4, N * L * 5 * 8, N * (1 + NM) * 8, N * NO * 8, N * 4};
     size_t fixed = S * 4 + 5 * SL + (b->liquid_water ? SL : 0) + (b->layer_kind ? S * L * 4 : 0) + F * 8 + T * 8 + NM * 8 +
-                   (b->substrate_kind != SMRT_SUBSTRATE_NONE ? 2 * FS * 8 + S * 8 : 0) + (pairs ? N * 8 : 0);
+                   (b->substrate_kind != SMRT_SUBSTRATE_NONE ? 2 * smrt_host::substrate_array_doubles(b) * 8 + S * 8 : 0) + (pairs ? N * 8 : 0);
     for (size_t v : out_bytes) fixed += v;
     if ((int64_t)fixed >= st->budget) {
         ctx->err = "the workspace budget of the successive_order solver is smaller than the buffers of the batch itself (" +

@@ -186,8 +186,8 @@ SMRT_DEV void so_prep_item(const SoBatch& b, long long i, int l) {
             fresnel_RvRh(el, cmk(so_stage(b, SO_EPS_RE, l + 1, i), so_stage(b, SO_EPS_IM, l + 1, i)), mu, &rv, &rh);
             rb = h ? rh : rv; tb = 1.0 - rb;
         } else if (b.sub_kind != SUB_NONE) {
-            if (b.sub_kind == SUB_FLAT) {
-                fresnel_RvRh(el, cmk(b.sub_p1[gp], b.sub_p2[gp]), mu, &rv, &rh);
+            if (b.sub_kind != SUB_REFLECTOR) {   // Flat, or a rough soil
+                substrate_RvRh(b, gp, s, frequency, el, mu, &rv, &rh);
                 rb = h ? rh : rv;
             } else rb = h ? b.sub_p2[gp] : b.sub_p1[gp];
             const double Ts = b.sub_T ? b.sub_T[s] : 0.0;
@@ -262,6 +262,8 @@ SMRT_DEV void so_sweep_pair(const SoBatch& b, long long i, double* lds) {
     if (!bad) {
         for (int l = 0; l < L; ++l) if (b.nstream[i * b.Lmax + l] < 2) bad = 1;
         if (n_air < 1) bad = 1;
+        // a Choudhury substrate out of its range under the last layer: the reference raises
+        if (!substrate_in_range(b, s, frequency, cmk(so_stage(b, SO_EPS_RE, L - 1, i), so_stage(b, SO_EPS_IM, L - 1, i)))) bad = 1;
     }
     for (int it = 0; it < nt; ++it) { const double um = cos(b.theta[it]); if (!(um > 0.0 && um <= 1.0)) bad = 1; }
     if (bad) {

@@ -49,18 +49,61 @@ def make_interface(inst_class_or_modulename=None, broadcast=True, **kwargs):
     return cls(**kwargs)
 
 
-def make_soil(substrate_model, permittivity_model, temperature, **kwargs):
-    """A substrate by name ("flat", "reflector", "iem_fung92", "geometrical_optics", "geometrical_optics_backscatter") or
-    class, with a numeric permittivity or a callable of (frequency[, temperature]) -- the part of
-    smrt/inputs/make_soil.py:41-139 that needs no soil dielectric model (those are outside the DORT path: give the
-    permittivity as a number or your own function)."""
-    from ..core.plugin import import_class
+def get_permittivity_function(permittivity_model):
+    """The soil or bedrock model of a name `<module>_permittivity_<x>` (smrt_amd.permittivity.<module>, or the same module of
+    a registered plugin package); the short names of the reference resolve to their `soil_permittivity_` form with a
+    DeprecationWarning (smrt/inputs/make_soil.py:276-300).  Anything that is not a name is returned as it is."""
+    import importlib
+    import warnings
 
-    if isinstance(permittivity_model, str):
-        raise SMRTError(f"the soil permittivity model '{permittivity_model}' is outside the scope of smrt_amd: give the "
-                        "permittivity as a number or as a function of (frequency, temperature)")
+    from ..core.plugin import _BUILTIN, user_plugin_package
+
+    if not isinstance(permittivity_model, str):
+        return permittivity_model
+    name = permittivity_model
+    if name in ("hut_epss", "dobson85", "dobson85_peplinski95", "montpetit2008"):
+        warnings.warn(f"The permittivity model '{name}' should be called with the prefix 'soil_permittivity_'. The new "
+                      f"recommended name is 'soil_permittivity_{name}'.", DeprecationWarning, stacklevel=3)
+        name = "soil_permittivity_" + name
+    if name.count("_permittivity_") != 1:
+        raise SMRTError(f"The permittivity model {name} has not a valid name. It must match the pattern "
+                        "<modulename>_permittivity_<something>.")
+    modulename = name.split("_permittivity_")[0]
+    for pkg in user_plugin_package + [_BUILTIN]:
+        try:
+            function = getattr(importlib.import_module(f"{pkg}.permittivity.{modulename}"), name, None)
+        except ImportError:
+            continue
+        if function is not None:
+            if name == "soil_permittivity_dobson85":
+                function(None, None, None, None, None)   # refused, with the two names that replace it
+            return function
+    raise SMRTError(f"Unable to find the permittivity model '{name}'")
+
+
+def make_soil_substrate(substrate_model, permittivity_model=None, temperature=FREEZING_POINT, moisture=None, sand=None,
+                        clay=None, dry_matter=None, **kwargs):
+    """A soil or bedrock substrate with the reference's signature (smrt/inputs/make_soil.py:60-111): `substrate_model` by
+    name ("flat", "reflector", "soil_wegmuller", "soil_qnh", "rough_choudhury79", "iem_fung92", "geometrical_optics",
+    "geometrical_optics_backscatter") or class; `permittivity_model` a number, a callable of (frequency[, temperature]) or
+    the name of a model of smrt_amd.permittivity.soil / .bedrock -- by default soil_permittivity_dobson85_peplinski95 --
+    which reads moisture, sand, clay, dry_matter and the temperature from the substrate.
+
+    make_soil_column and make_soil_layer are not here: a soil LAYER needs a permittivity model on the layer's side (the
+    device computes the layers' electromagnetics itself), which is a piece of work of its own."""
+    from ..core.plugin import import_class
+    from ..permittivity.soil import soil_permittivity_dobson85_peplinski95
+
+    permittivity_model = get_permittivity_function(permittivity_model)
+    if permittivity_model is None:
+        permittivity_model = soil_permittivity_dobson85_peplinski95
     cls = import_class("substrate", substrate_model) if isinstance(substrate_model, str) else substrate_model
-    return cls(temperature=temperature, permittivity_model=permittivity_model, **kwargs)
+    soil = dict(moisture=moisture, sand=sand, clay=clay, dry_matter=dry_matter)
+    return cls(temperature=temperature, permittivity_model=permittivity_model,
+               **{k: v for k, v in soil.items() if v is not None}, **kwargs)
+
+
+make_soil = make_soil_substrate
 
 
 def make_snow_layer(layer_thickness, microstructure_model, density, temperature=FREEZING_POINT, **kwargs):

@@ -17,12 +17,13 @@ from collections.abc import Mapping
 
 import numpy as np
 
-from .._native import STATUS_MESSAGES, BatchOutput, DortContext, PackedBatch, device_count
+from .._native import SOIL_KINDS, STATUS_MESSAGES, BatchOutput, DortContext, PackedBatch, device_count, status_message
 from ..core.error import SMRTError, smrt_warn
 from ..core.globalconstants import C_SPEED
 from ..core.foreign import result_factory
 from ..core.result import LabeledArray, make_result
 from ..core.snowpack import Snowpack, substrate_kind
+from ..core.substrate import batch_permittivities
 from ..interface.flat import Flat
 
 # the row blocks and the stacked columns of the last group that was packed (DORT._pack): a repeated Model.run on the same,
@@ -234,9 +235,12 @@ class DORT(object):
             key = (sensor.mode, tuple(np.round(angles, 12)), float(np.ravel(sensor.phi)[0]))
             s_code[k] = sensor_keys.setdefault(key, len(sensor_keys))
         p_code = np.empty(len(packs), np.int64)
+        # (the rough soils are device kinds in passive mode and "host" objects in active mode; a run mixing the two modes keeps
+        # the passive kinds apart, which only splits groups)
+        mode = "A" if all(s.mode == "A" for s in sensors) else "P"
         for k, sp in enumerate(packs):
             on_host = not isinstance(emmodel_names, str) and any(not isinstance(e, str) for e in emmodel_names[k])
-            key = (substrate_kind(sp.substrate), id(sp.atmosphere) if sp.atmosphere is not None else None, on_host)
+            key = (substrate_kind(sp.substrate, mode), id(sp.atmosphere) if sp.atmosphere is not None else None, on_host)
             p_code[k] = pack_keys.setdefault(key, len(pack_keys))
         freq = np.array([float(s.frequency) for s in sensors])
         code = s_code[sens_idx] * len(pack_keys) + p_code[pack_idx]
@@ -255,7 +259,7 @@ class DORT(object):
             bad = np.nonzero(out.status != 0)[0]
             if len(bad) and self.error_handling == "exception":
                 st = int(out.status[bad[0]])
-                raise SMRTError(STATUS_MESSAGES.get(st, f"DORT failed with status {st}"))
+                raise SMRTError(status_message(batch, st, STATUS_MESSAGES.get(st, f"DORT failed with status {st}")))
             sol.add_group(sel, out, sp0, (u_packs, np.array(batch.n_layers, np.int64), np.array(batch.thickness, float)))
         return sol
 
@@ -347,9 +351,16 @@ class DORT(object):
         mode = sensor0.mode
         substrate = atmosphere = None
         sub0 = sps[0].substrate
-        if sub0 is not None and substrate_kind(sub0) == "host":
+        if sub0 is not None and substrate_kind(sub0, mode) == "host":
             substrate = self._substrates_on_host(sensor0, sps, freqs, cols, nl, emmodel_names, layer_kind, host,
                                                      scalars=scalars, liquid_water=liquid_water)
+        elif sub0 is not None and sub0.device_kind in SOIL_KINDS:
+            # a rough soil, evaluated per stream on the device: the soil permittivity per (frequency, snowpack) -- a named model
+            # once per frequency on the columns of the group -- and the four numbers of the roughness model per snowpack
+            eps = batch_permittivities([sp.substrate for sp in sps], freqs)
+            tails = np.array([sp.substrate.device_tail() for sp in sps], float)   # (S, 2, 2)
+            ts = [sp.substrate.temperature if sp.substrate.temperature is not None else 0.0 for sp in sps]
+            substrate = (sub0.device_kind, eps.real, eps.imag, ts, tails[:, 0], tails[:, 1])
         elif sub0 is not None:  # one kind per group; permittivity / reflection per (frequency, snowpack)
             q = np.array([[sp.substrate.device_params(f) for sp in sps] for f in freqs])  # (F, S, 2)
             ts = [sp.substrate.temperature if sp.substrate.temperature is not None else 0.0 for sp in sps]

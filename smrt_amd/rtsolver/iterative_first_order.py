@@ -77,7 +77,7 @@ class IterativeFirstOrder(SolverBase):
 
     def _snowpack_key(self, sp, on_host):
         self._refuse_atmosphere(sp)
-        return sp, (substrate_kind(sp.substrate), on_host)
+        return sp, (substrate_kind(sp.substrate, "A"), on_host)
 
     def _solve_indexed(self, sensors, packs, sens_idx, pack_idx, emmodel_names, packer=None):
         sol = SolverBase._solve_indexed(self, sensors, packs, sens_idx, pack_idx, emmodel_names, packer)
@@ -156,7 +156,7 @@ class IterativeFirstOrder(SolverBase):
         (batch.host_layer); otherwise `layers_of(batch)` -- DortContext.first_order_layers: one run of the solver without
         extras, of which only layer_out [n_pairs, Lmax, 5] is read -- gives the device's."""
         rough = [[i for i, itf in enumerate(sp.interfaces) if not isinstance(itf, Flat)] for sp in sps]
-        host_sub = [sp.substrate is not None and substrate_kind(sp.substrate) == "host" for sp in sps]
+        host_sub = [sp.substrate is not None and substrate_kind(sp.substrate, "A") == "host" for sp in sps]
         ems = packer.host_emmodels
         if not any(rough) and not any(host_sub) and ems is None:
             return None

@@ -144,7 +144,7 @@ class IterativeSecondOrder(IterativeFirstOrder):
 
     def _substrate_modes(self, ctx, batch, sensor0, sps, freqs):
         subs = [sp.substrate for sp in sps]
-        rough = [s is not None and substrate_kind(s) == "host" and callable(getattr(s, "ft_even_diffuse_reflection_matrix", None))
+        rough = [s is not None and substrate_kind(s, "A") == "host" and callable(getattr(s, "ft_even_diffuse_reflection_matrix", None))
                  for s in subs]
         if not any(rough):
             return None

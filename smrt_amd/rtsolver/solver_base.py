@@ -15,7 +15,7 @@ import types
 import numpy as np
 
 from . import dort
-from .._native import STATUS_MESSAGES
+from .._native import STATUS_MESSAGES, status_message
 from ..core.error import SMRTError
 from ..core.globalconstants import C_SPEED
 from ..core.result import LabeledArray
@@ -183,7 +183,8 @@ class SolverBase(object):
             bad = np.argwhere(out.status != 0)
             if len(bad) and self.error_handling == "exception":
                 at = tuple(bad[0])
-                raise SMRTError(self._status_message(out, at, int(out.status[at])))
+                status = int(out.status[at])   # (status 5 on a Choudhury substrate names the validity range of the model)
+                raise SMRTError(status_message(g.batch, status, self._status_message(out, at, status)))
             sol.add_group(sel, out, g.sps[0], (u_packs, np.array(g.batch.n_layers, np.int64), np.array(g.batch.thickness, float)))
             self._after_group(g, out)
         return sol

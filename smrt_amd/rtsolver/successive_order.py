@@ -30,6 +30,7 @@ import numpy as np
 
 from ..core.error import SMRTError
 from ..core.snowpack import Snowpack, substrate_kind
+from ..core.substrate import PASSIVE_DEVICE_KINDS
 from ..substrate.transparent import Transparent
 from .dort import _Solution as _DortSolution, get_context
 from .solver_base import RefusingPacker, SolverBase, check_error_handling
@@ -121,7 +122,7 @@ class SuccessiveOrder(SolverBase):
             raise SMRTError("the successive_order solver takes Flat interfaces only: rough interfaces are not implemented.")
         if isinstance(sp.substrate, Transparent):
             return Snowpack(layers=sp.layers, interfaces=sp.interfaces, substrate=None)
-        if sp.substrate is not None and substrate_kind(sp.substrate) not in ("flat", "reflector"):
+        if sp.substrate is not None and substrate_kind(sp.substrate) not in ("flat", "reflector") + PASSIVE_DEVICE_KINDS:
             raise SMRTError("the successive_order solver takes no substrate, a Flat, a Reflector or a transparent one: "
                             f"{type(sp.substrate).__name__} is not implemented.")
         return sp
