@@ -240,7 +240,39 @@ typedef struct smrt_batch {
     /* layers of kind SMRT_EM_IBA_HOST: [F * S][Lmax] the coefficient of IBA's phase matrix (see SMRT_EM_IBA_HOST), indexed
      * like host_layer by the global pair f * S + s; null when no layer has that kind */
     const double* host_iba_coeff;
+    /* Rough boundaries evaluated on the device (SMRT_ROUGH_*; smrt_amd/csrc/rough_boundary_kernel.hpp): the library builds what
+     * the caller of host_interface* / host_substrate* would hand over, from the layer inputs, for the pairs of the upload.
+     *   rough_kind   [S][n_layers_max + 1] int32: entry l < n_layers is the interface ON TOP of layer l (0: the surface), entry
+     *                n_layers the substrate; SMRT_ROUGH_NONE: not rough on the device (Flat interface; the batch's substrate_kind);
+     *   rough_params [S][n_layers_max + 1][4]: geometrical_optics and geometrical_optics_backscatter: mean square slope, shadow
+     *                correction (0 / 1); iem_fung92: rms height (m), correlation length (m), autocorrelation function
+     *                (0 exponential, 1 gaussian), series truncation.  A NaN parameter gives the pair NaN matrices.
+     * A rough substrate goes with substrate_kind = SMRT_SUBSTRATE_FLAT: substrate_p1 + i substrate_p2 is its permittivity,
+     * substrate_temperature its temperature; every snowpack of the batch then has one.  Not together with host_interface_slot,
+     * SMRT_SUBSTRATE_HOST or process_coherent_layers; m_max <= SMRT_ROUGH_M_MAX in active mode.  NULL rough_kind: nothing
+     * of this runs. */
+    const int32_t* rough_kind;
+    const double* rough_params;
 } smrt_batch;
+
+/* rough_kind entries */
+#define SMRT_ROUGH_NONE 0
+#define SMRT_ROUGH_GEOMETRICAL_OPTICS 1            /* smrt/interface/geometrical_optics.py: bistatic reflection and transmission */
+#define SMRT_ROUGH_GEOMETRICAL_OPTICS_BACKSCATTER 2 /* geometrical_optics_backscatter.py: the lobe + 1 - hemispherical reflectivity */
+#define SMRT_ROUGH_IEM_FUNG92 3                    /* iem_fung92.py: Kirchhoff coherent part + the backscatter series */
+#define SMRT_ROUGH_M_MAX 4                         /* largest m_max the builder is instantiated for */
+
+/* The builder alone, for tests and tools: uploads the batch (all its pairs), builds, and copies back what the solve would read
+ * -- slot [F * S][n_layers_max], itf [F * S][slots][modes][4][NE * NE], itf_coh [F * S][slots][4][NE], sub [F * S][modes][NE * NE],
+ * sub_coh [F * S][modes][NE] (layouts of host_interface* / host_substrate* above; any pointer may be NULL).  The number of slots
+ * is the largest count of rough interfaces in a snowpack of the batch.  Returns that number, or -1.
+ * smrt_dort_rough_info: info[0] = SMRT_ROUGH_M_MAX (the capability), and of the last upload: [1] slots, [2] HIP-event time of
+ * the builder kernels (ms), [3] bytes of matrices built on the device, [4] bytes of host_interface / host_substrate matrices
+ * copied from the caller, [5] bytes of device memory the builder's matrices may take now (free memory plus what its buffers
+ * hold already).  Returns the number of entries of the description; at most n are written. */
+int32_t smrt_dort_rough_matrices(smrt_dort_ctx* ctx, const smrt_batch* batch, int32_t* slot, double* itf, double* itf_coh,
+                                 double* sub, double* sub_coh);
+int32_t smrt_dort_rough_info(smrt_dort_ctx* ctx, double* info, int32_t n);
 
 /* Sizes of the output rows (doubles per pair). Passive: Tb[pol V,H][theta].  Active: I[pol][pol_inc][theta_inc]
  * with 3 x 3 polarisations V,H,U (layout of Result.data in the reference, rtsolver_utils.py:327-332). */

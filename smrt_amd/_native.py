@@ -98,7 +98,20 @@ class SmrtBatch(C.Structure):
         ("host_interface_slots", C.c_int32),
         ("liquid_water", C.POINTER(C.c_double)),
         ("host_iba_coeff", C.POINTER(C.c_double)),
+        ("rough_kind", C.POINTER(C.c_int32)),
+        ("rough_params", C.POINTER(C.c_double)),
     ]
+
+
+# rough boundaries the device evaluates itself (SMRT_ROUGH_*): the device_kind of the interface / substrate classes
+ROUGH_CODES = {"geometrical_optics": 1, "geometrical_optics_backscatter": 2, "iem_fung92": 3}
+ROUGH_M_MAX = 4   # SMRT_ROUGH_M_MAX
+
+
+def rough_matrix_bytes(n_pairs, slots, has_substrate, n_max_stream, modes):
+    """Bytes of the dense matrices the device builds for the rough boundaries of n_pairs pairs (include/smrt_dort.h)."""
+    ne = 3 * int(n_max_stream)
+    return 8 * int(n_pairs) * int(modes) * ne * ne * (4 * int(slots) + (1 if has_substrate else 0))
 
 
 def _dptr(a):
@@ -113,7 +126,7 @@ class PackedBatch:
                  emmodel="iba", microstructure="exponential", mode="P", n_max_stream=32, m_max=2,
                  phase_normalization="auto", rayleigh_jeans=False, phi=np.pi, substrate=None, atmosphere=None,
                  prune_deep_snowpack=None, layer_kind=None, host_emmodel=None, process_coherent_layers=False,
-                 host_interfaces=None, liquid_water=None, host_scalars=None):
+                 host_interfaces=None, liquid_water=None, host_scalars=None, rough=None):
         """substrate: None or (kind, p1[F][S], p2[F][S], temperature[S]) with kind "flat" (p1 + i p2 = permittivity) or
         "reflector" (p1, p2 = specular reflection V, H); temperature <= 0 or NaN = no emission.  For the kinds
         "soil_wegmuller", "soil_qnh", "rough_choudhury79" (passive mode) two more elements, tail1[S][2] and tail2[S][2]: p1 + i p2
@@ -238,6 +251,14 @@ class PackedBatch:
             s.host_interface_slot = self.host_interface_slot.ctypes.data_as(C.POINTER(C.c_int32))
             s.host_interface, s.host_interface_coh = _dptr(self.host_interface), _dptr(self.host_interface_coh)
             s.host_interface_slots = nslots
+        if rough is not None:
+            # rough boundaries evaluated on the device: (kind[S][Lmax + 1] int (ROUGH_CODES, 0: not rough),
+            # params[S][Lmax + 1][4]); entry l is the interface on top of layer l, entry n_layers the substrate, which then
+            # travels as substrate=("flat", Re eps, Im eps, temperature)
+            self.rough_kind = np.ascontiguousarray(np.asarray(rough[0], dtype=np.int32).reshape(S, Lmax + 1))
+            self.rough_params = np.ascontiguousarray(np.asarray(rough[1], dtype=np.float64).reshape(S, Lmax + 1, 4))
+            s.rough_kind = self.rough_kind.ctypes.data_as(C.POINTER(C.c_int32))
+            s.rough_params = _dptr(self.rough_params)
         self.struct = s
 
     @property
@@ -654,6 +675,11 @@ def load_library():
                                             C.c_double, P(C.c_double), C.c_int32, P(C.c_double), C.c_int32, C.c_int32, C.c_int32,
                                             P(C.c_double)]
     lib.smrt_dort_ft_even_phase.restype = C.c_int32
+    lib.smrt_dort_rough_matrices.argtypes = [C.c_void_p, P(SmrtBatch), P(C.c_int32), P(C.c_double), P(C.c_double), P(C.c_double),
+                                             P(C.c_double)]
+    lib.smrt_dort_rough_matrices.restype = C.c_int32
+    lib.smrt_dort_rough_info.argtypes = [C.c_void_p, P(C.c_double), C.c_int32]
+    lib.smrt_dort_rough_info.restype = C.c_int32
     lib.smrt_dort_pair_cost.argtypes = [C.c_void_p, P(C.c_double)]
     lib.smrt_dort_pair_cost.restype = C.c_int32
     lib.smrt_dort_launch_info.argtypes = [C.c_void_p, P(C.c_int64), C.c_int32]
@@ -928,7 +954,32 @@ EXPORTED_SYMBOLS = [
     "smrt_lrm_kernel_ms", "smrt_lrm_abi", "smrt_lrm_layers",
     "smrt_sar_out_stride", "smrt_sar_run_pairs", "smrt_sar_upload_pairs", "smrt_sar_launch", "smrt_sar_sync", "smrt_sar_download",
     "smrt_sar_kernel_ms", "smrt_sar_abi",
+    "smrt_dort_rough_matrices", "smrt_dort_rough_info",
 ]
+
+
+class RoughMatrices:
+    """What the solve reads for the rough boundaries of a batch (include/smrt_dort.h: host_interface*, host_substrate*), as
+    the device builder or its CPU build fills it: slot [FS][Lmax] (-1: Flat), itf [FS][slots][modes][4][NE][NE],
+    itf_coh [FS][slots][4][NE], sub [FS][modes][NE][NE], sub_coh [FS][modes][NE]."""
+
+    def __init__(self, batch):
+        s = batch.struct
+        S, Lmax = int(s.n_snowpacks), int(s.n_layers_max)
+        FS, ne = batch.n_pairs, 3 * int(s.n_max_stream)
+        nm = int(s.m_max) + 1 if batch.mode == "A" else 1
+        kinds = batch.rough_kind
+        self.slots = max(int(np.count_nonzero(kinds[k, :batch.n_layers[k]])) for k in range(S))
+        self.has_substrate = bool(kinds[0, batch.n_layers[0]])
+        self.slot = -np.ones((FS, Lmax), np.int32)
+        self.itf = np.zeros((FS, self.slots, nm, 4, ne, ne))
+        self.itf_coh = np.zeros((FS, self.slots, 4, ne))
+        self.sub = np.zeros((FS, nm, ne, ne))
+        self.sub_coh = np.zeros((FS, nm, ne))
+
+    def pointers(self):
+        return (self.slot.ctypes.data_as(C.POINTER(C.c_int32)), _dptr(self.itf), _dptr(self.itf_coh), _dptr(self.sub),
+                _dptr(self.sub_coh))
 
 
 class BatchOutput:
@@ -1327,6 +1378,32 @@ class DortContext:
                 float(p1), float(p2), _dptr(mu_s), len(mu_s), _dptr(mu_i), len(mu_i), int(m_max), int(npol), _dptr(out)),
                 "smrt_dort_ft_even_phase")
         return out
+
+    # ---- rough boundaries evaluated on the device (smrt_batch.rough_kind) ------------------------------------------------
+    rough_on_device = True                 # DORT packs rough_kind / rough_params for a context that says so
+
+    @property
+    def rough_workspace_budget(self):
+        """Bytes of rough matrices one launch may build; DORT splits a group beyond it.  Half of what the device has free for
+        them (the solve's own workspace takes its share of the rest), 4 GiB at the most."""
+        v = (C.c_double * 6)()
+        self._lib.smrt_dort_rough_info(self._h, v, 6)
+        return min(4 << 30, int(0.5 * v[5]))
+
+    def rough_matrices(self, batch: PackedBatch) -> RoughMatrices:
+        """The builder alone on every pair of the batch, its matrices copied back (smrt_dort_rough_matrices)."""
+        o = RoughMatrices(batch)
+        with self.lock:
+            rc = self._lib.smrt_dort_rough_matrices(self._h, C.byref(batch.struct), *o.pointers())
+            self._check(0 if rc >= 0 else -1, "smrt_dort_rough_matrices")
+        return o
+
+    def rough_info(self):
+        """Of the last upload: slots, the builder kernels' HIP-event time (ms), bytes of rough matrices built on the device,
+        bytes of rough matrices copied from the host (smrt_dort_rough_info); m_max_limit: the capability."""
+        v = (C.c_double * 5)()
+        self._lib.smrt_dort_rough_info(self._h, v, 5)
+        return dict(m_max_limit=int(v[0]), slots=int(v[1]), builder_ms=float(v[2]), built_bytes=int(v[3]), host_matrix_bytes=int(v[4]))
 
     def pair_cost(self):
         """Sum of N_l^3 per pair of the uploaded batch (before solving it): what the work is sharded by."""

@@ -12,10 +12,12 @@ def substrate_kind(substrate, mode="P"):
     itself, "host" for any other object that speaks the reference's substrate protocol (smrt/core/interface.py:169-240:
     evaluated in Python, handed to the device as dense reflection matrices), None for anything else.  The three soil models
     are device kinds in passive mode only: for a sensor of mode "A" they are "host" objects."""
-    from .substrate import PASSIVE_DEVICE_KINDS
+    from .substrate import PASSIVE_DEVICE_KINDS, ROUGH_DEVICE_KINDS
 
     kind = getattr(substrate, "device_kind", None)
-    if kind is None or (mode == "A" and kind in PASSIVE_DEVICE_KINDS):
+    # (the rough models DORT evaluates on the device are "host" objects here: whether a group takes the device route is
+    # DORT's decision, rtsolver/dort.py:_rough_on_device, and every other solver evaluates them through the protocol)
+    if kind is None or kind in ROUGH_DEVICE_KINDS or (mode == "A" and kind in PASSIVE_DEVICE_KINDS):
         kind = "host" if callable(getattr(substrate, "specular_reflection_matrix", None)) else None
     return kind
 

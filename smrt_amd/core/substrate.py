@@ -10,6 +10,8 @@ SOIL_ARGUMENTS = ("moisture", "sand", "clay", "dry_matter")
 # substrates the device evaluates in passive mode only: Fresnel times a roughness factor per polarisation
 # (include/smrt_dort.h: SMRT_SUBSTRATE_SOIL_WEGMULLER, _SOIL_QNH, _ROUGH_CHOUDHURY); in active mode they are "host" objects
 PASSIVE_DEVICE_KINDS = ("soil_wegmuller", "soil_qnh", "rough_choudhury79")
+# rough models DORT evaluates on the device, as interfaces and as substrates (include/smrt_dort.h: SMRT_ROUGH_*)
+ROUGH_DEVICE_KINDS = ("geometrical_optics", "geometrical_optics_backscatter", "iem_fung92")
 
 
 class SubstrateBase:

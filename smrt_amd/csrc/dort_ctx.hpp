@@ -9,6 +9,7 @@
 #include "dort_layout.hpp"
 
 namespace smrt { struct PhaseRequest; struct FoBatch; }
+struct smrt_batch;
 
 struct DevBuf {
     void* p = nullptr;
@@ -93,6 +94,9 @@ struct smrt_dort_ctx {
     struct SecondOrderState* second_order = nullptr;
     struct LrmState* lrm = nullptr;
     struct SarState* sar = nullptr;
+    // rough boundaries evaluated on the device (k_rough.hip): the builder's buffers, and what the last upload did
+    struct RoughState* rough = nullptr;
+    struct { int slots = 0, has_sub = 0; float ms = 0.f; size_t built_bytes = 0, host_matrix_bytes = 0; } rough_info;
 };
 
 #ifndef SMRT_JACOBI_NT
@@ -145,6 +149,10 @@ void multifresnel_release(smrt_dort_ctx* ctx);
 void second_order_release(smrt_dort_ctx* ctx);
 void lrm_release(smrt_dort_ctx* ctx);
 void sar_release(smrt_dort_ctx* ctx);
+// k_rough.hip: the rough boundaries of a batch with rough_kind -- builds host_interface* / host_substrate* on the device for the
+// pairs of the upload, points `d` at them and waits; 0, or -1 with ctx->err set
+int rough_prepare(smrt_dort_ctx* ctx, const smrt_batch* b, smrt::DevBatch& d);
+void rough_release(smrt_dort_ctx* ctx);
 // first_order.hip: the resident batch of the first-order solver as its kernels get it (null: nothing uploaded); the
 // second-order solver sets its carry pointer and reads the staging rows and outputs
 smrt::FoBatch* first_order_resident(smrt_dort_ctx* ctx);

@@ -211,6 +211,7 @@ void smrt_dort_destroy(smrt_dort_ctx* ctx) {
     smrt_launch::lrm_release(ctx);
     smrt_launch::sar_release(ctx);
     smrt_launch::second_order_release(ctx);
+    smrt_launch::rough_release(ctx);
     if (ctx->ev0) (void)hipEventDestroy(ctx->ev0);
     if (ctx->ev1) (void)hipEventDestroy(ctx->ev1);
     for (int k = 0; k < 4; ++k) {
@@ -429,7 +430,7 @@ static int32_t upload_impl(smrt_dort_ctx* ctx, const smrt_batch* b, int64_t pair
     // interfaces with T = 1 - R (no coherent slabs), no host-evaluated dense substrate
     {
         const bool supported = !ctx->gmem_path && ctx->split && ctx->finish2 && !ctx->active && ctx->chunk_pairs > 0 &&
-                               !b->process_coherent_layers && b->substrate_kind != SUB_HOST && !b->host_interface_slot;
+                               !b->process_coherent_layers && b->substrate_kind != SUB_HOST && !b->host_interface_slot && !b->rough_kind;
         int want = (ctx->finish_mode == 2) ? -1 : ctx->finish_mode;
         if (const char* e = getenv("SMRT_DORT_FINISH_REG")) want = atoi(e) ? 1 : 0;
         ctx->finish_reg_lds_bytes = sizeof(double) * (size_t)finish_reg_lds_doubles(b->n_max_stream, b->n_layers_max);
@@ -470,7 +471,7 @@ static int32_t upload_impl(smrt_dort_ctx* ctx, const smrt_batch* b, int64_t pair
     // passive mode under the same conditions
     {
         const bool supported = ctx->gmem_split && !ctx->big && !ctx->active && plan.NMAX <= 128 && ctx->chunk_pairs > 0 &&
-                               !b->process_coherent_layers && b->substrate_kind != SUB_HOST && !b->host_interface_slot;
+                               !b->process_coherent_layers && b->substrate_kind != SUB_HOST && !b->host_interface_slot && !b->rough_kind;
         int want = (ctx->finish_mode == 2) ? 1 : ctx->finish_mode;
         if (const char* e = getenv("SMRT_DORT_FINISH_STRIP")) want = atoi(e) ? 1 : 0;
         ctx->finish_strip_lds_bytes = sizeof(double) * (size_t)finish_strip_lds_doubles(b->n_max_stream, b->n_layers_max);
@@ -519,17 +520,23 @@ static int32_t upload_impl(smrt_dort_ctx* ctx, const smrt_batch* b, int64_t pair
         if (upload_array(ctx, ctx->d_hostphase, b->host_phase, sizeof(double) * PL * host_modes * 2 * host_ne * host_ne)) return -1;
     }
     const size_t FS = (size_t)b->n_snowpacks * b->n_frequencies;
+    ctx->rough_info = {};
     if (b->host_interface_slot) {   // rough interfaces evaluated by the caller
         const size_t ne = 3 * (size_t)b->n_max_stream, nm = ctx->active ? (size_t)b->m_max + 1 : 1, ns = (size_t)b->host_interface_slots;
         if (upload_array(ctx, ctx->d_itfslot, b->host_interface_slot, sizeof(int32_t) * FS * b->n_layers_max)) return -1;
         if (upload_array(ctx, ctx->d_itf, b->host_interface, sizeof(double) * FS * ns * nm * 4 * ne * ne)) return -1;
         if (upload_array(ctx, ctx->d_itfcoh, b->host_interface_coh, sizeof(double) * FS * ns * 4 * ne)) return -1;
+        ctx->rough_info.host_matrix_bytes += sizeof(double) * FS * ns * nm * 4 * ne * ne;
     }
     if (b->substrate_kind == SMRT_SUBSTRATE_HOST) {   // dense reflection matrices of a rough substrate, evaluated by the caller
         const size_t ne = 3 * (size_t)b->n_max_stream, nm = ctx->active ? (size_t)b->m_max + 1 : 1;
         if (upload_array(ctx, ctx->d_sub1, b->host_substrate, sizeof(double) * FS * nm * ne * ne)) return -1;
         if (upload_array(ctx, ctx->d_sub2, b->host_substrate_coh, sizeof(double) * FS * nm * ne)) return -1;
         if (b->substrate_temperature && upload_array(ctx, ctx->d_subT, b->substrate_temperature, sizeof(double) * b->n_snowpacks)) return -1;
+        ctx->rough_info.host_matrix_bytes += sizeof(double) * FS * nm * ne * ne;
+    } else
+    if (smrt_host::rough_substrate(b)) {   // a rough substrate built on the device: its permittivity goes to the builder (rough_prepare)
+        if (upload_array(ctx, ctx->d_subT, b->substrate_temperature, sizeof(double) * b->n_snowpacks)) return -1;
     } else
     if (b->substrate_kind != SMRT_SUBSTRATE_NONE) {
         const size_t sub_doubles = smrt_host::substrate_array_doubles(b);   // (the rough soils: + [S][2] parameters, smrt_dort.h)
@@ -612,6 +619,7 @@ static int32_t upload_impl(smrt_dort_ctx* ctx, const smrt_batch* b, int64_t pair
         d.rayleigh_direct = (!ctx->active && (ctx->finish_strip || ctx->finish_strip4) && ctx->stage.Linv && may_hold && !(e && atoi(e) == 0)) ? 1 : 0;
     }
     ctx->lds_bytes = lds;
+    if (b->rough_kind && smrt_launch::rough_prepare(ctx, b, d)) return -1;
     HIPCHK(hipStreamSynchronize(ctx->stream));  // the staging vector `gl` and the caller's arrays may go away
     ctx->uploaded = true;
     // Dispatch order: inside every chunk the workgroups take the pairs sorted by their estimated cost (sum of N_l^3 from the
@@ -660,11 +668,43 @@ int32_t smrt_dort_abi(int32_t* out, int32_t capacity) {
         SMRT_OFF(atm_tb_up), SMRT_OFF(atm_transmittance), SMRT_OFF(prune_optical_depth), SMRT_OFF(layer_kind),
         SMRT_OFF(host_layer), SMRT_OFF(host_streams), SMRT_OFF(host_phase), SMRT_OFF(process_coherent_layers),
         SMRT_OFF(host_substrate), SMRT_OFF(host_substrate_coh), SMRT_OFF(host_interface_slot), SMRT_OFF(host_interface),
-        SMRT_OFF(host_interface_coh), SMRT_OFF(host_interface_slots), SMRT_OFF(liquid_water), SMRT_OFF(host_iba_coeff)};
+        SMRT_OFF(host_interface_coh), SMRT_OFF(host_interface_slots), SMRT_OFF(liquid_water), SMRT_OFF(host_iba_coeff),
+        SMRT_OFF(rough_kind), SMRT_OFF(rough_params)};
 #undef SMRT_OFF
     const int32_t n = (int32_t)(sizeof(desc) / sizeof(desc[0]));
     for (int32_t i = 0; out && i < n && i < capacity; ++i) out[i] = desc[i];
     return n;
+}
+
+int32_t smrt_dort_rough_matrices(smrt_dort_ctx* ctx, const smrt_batch* b, int32_t* slot, double* itf, double* itf_coh, double* sub,
+                                 double* sub_coh) {
+    if (!ctx) return -1;
+    if (!b || !b->rough_kind) { ctx->err = "smrt_dort_rough_matrices needs a batch with rough_kind"; return -1; }
+    if (upload_impl(ctx, b, 0, -1, nullptr)) return -1;
+    const size_t FS = (size_t)b->n_snowpacks * b->n_frequencies, ne = 3 * (size_t)b->n_max_stream, nm = ctx->active ? (size_t)b->m_max + 1 : 1;
+    const size_t ns = (size_t)ctx->rough_info.slots;
+    if (ns > 0) {
+        if (slot) HIPCHK(hipMemcpy(slot, ctx->d_itfslot.p, sizeof(int32_t) * FS * b->n_layers_max, hipMemcpyDeviceToHost));
+        if (itf) HIPCHK(hipMemcpy(itf, ctx->d_itf.p, sizeof(double) * FS * ns * nm * 4 * ne * ne, hipMemcpyDeviceToHost));
+        if (itf_coh) HIPCHK(hipMemcpy(itf_coh, ctx->d_itfcoh.p, sizeof(double) * FS * ns * 4 * ne, hipMemcpyDeviceToHost));
+    }
+    if (ctx->rough_info.has_sub) {
+        if (sub) HIPCHK(hipMemcpy(sub, ctx->d_sub1.p, sizeof(double) * FS * nm * ne * ne, hipMemcpyDeviceToHost));
+        if (sub_coh) HIPCHK(hipMemcpy(sub_coh, ctx->d_sub2.p, sizeof(double) * FS * nm * ne, hipMemcpyDeviceToHost));
+    }
+    return (int32_t)ns;
+}
+
+int32_t smrt_dort_rough_info(smrt_dort_ctx* ctx, double* info, int32_t n) {
+    if (!ctx || !info || n < 0) return -1;
+    // [5]: bytes the builder may take for its matrices -- what it holds already plus the device's free memory
+    size_t free_b = 0, total_b = 0;
+    if (n > 5 && hipMemGetInfo(&free_b, &total_b) != hipSuccess) free_b = 0;
+    const double v[6] = {(double)SMRT_ROUGH_M_MAX, (double)ctx->rough_info.slots, (double)ctx->rough_info.ms,
+                         (double)ctx->rough_info.built_bytes, (double)ctx->rough_info.host_matrix_bytes,
+                         (double)(free_b + ctx->d_itf.cap + ctx->d_sub1.cap)};
+    for (int k = 0; k < n && k < 6; ++k) info[k] = v[k];
+    return 6;
 }
 
 int32_t smrt_dort_launch(smrt_dort_ctx* ctx, void* out_dev, void* status_dev) {

@@ -112,6 +112,37 @@ inline size_t substrate_array_doubles(const smrt_batch* b) {
     return (size_t)b->n_frequencies * b->n_snowpacks + (is_soil_substrate(b->substrate_kind) ? 2 * (size_t)b->n_snowpacks : 0);
 }
 
+// Rough boundaries evaluated on the device: is the substrate of the batch one of them (entry n_layers of the first snowpack;
+// validate() holds the others to the same answer)?
+inline bool rough_substrate(const smrt_batch* b) {
+    return b->rough_kind && b->n_layers && b->rough_kind[b->n_layers[0]] != SMRT_ROUGH_NONE;
+}
+
+inline const char* refuse_rough(const smrt_batch* b) {
+    if (!b->rough_kind) return nullptr;
+    if (!b->rough_params) return "rough_kind needs rough_params";
+    if (b->host_interface_slot || b->substrate_kind == SMRT_SUBSTRATE_HOST)
+        return "rough_kind cannot be combined with host_interface_slot or SMRT_SUBSTRATE_HOST: the rough boundaries of a batch take one route";
+    if (b->process_coherent_layers)
+        return "rough_kind cannot be combined with process_coherent_layers: hand the rough boundaries over as host_interface / SMRT_SUBSTRATE_HOST";
+    if (b->mode == SMRT_MODE_ACTIVE && b->m_max > SMRT_ROUGH_M_MAX)
+        return "rough_kind: m_max beyond SMRT_ROUGH_M_MAX, the largest the rough-boundary kernels are instantiated for";
+    const bool sub = rough_substrate(b);
+    if (sub && b->substrate_kind != SMRT_SUBSTRATE_FLAT)
+        return "a rough substrate on the device needs substrate_kind = SMRT_SUBSTRATE_FLAT (its permittivity in substrate_p1 / substrate_p2)";
+    const long long W = (long long)b->n_layers_max + 1;
+    for (int s = 0; s < b->n_snowpacks; ++s) {
+        if (b->n_layers[s] < 1 || b->n_layers[s] > b->n_layers_max) return "n_layers out of range";
+        for (int l = 0; l <= b->n_layers[s]; ++l) {
+            const int k = b->rough_kind[s * W + l];
+            if (k < SMRT_ROUGH_NONE || k > SMRT_ROUGH_IEM_FUNG92) return "unknown rough_kind entry";
+        }
+        if ((b->rough_kind[s * W + b->n_layers[s]] != SMRT_ROUGH_NONE) != sub)
+            return "rough_kind: the substrates of a batch are rough on the device for every snowpack or for none";
+    }
+    return nullptr;
+}
+
 inline const char* validate(const smrt_batch* b) {
     if (!b) return "null batch";
     if (b->n_snowpacks <= 0 || b->n_frequencies <= 0 || b->n_layers_max <= 0) return "empty batch";
@@ -172,7 +203,7 @@ inline const char* validate(const smrt_batch* b) {
     }
     if ((b->atm_tb_down != nullptr) != (b->atm_tb_up != nullptr) || (b->atm_tb_down != nullptr) != (b->atm_transmittance != nullptr))
         return "atmosphere arrays must be given together";
-    return nullptr;
+    return refuse_rough(b);
 }
 
 // What the solvers beside DORT refuse alike (solver_refusals.hpp holds each solver's own checks, and calls these between
@@ -207,6 +238,8 @@ inline const char* refuse_emmodel(int em, int ms, const SolverAccepts& a) {
 
 // the model codes, the input arrays, n_layers and the layer_kind entries (a non-empty batch)
 inline const char* refuse_inputs(const smrt_batch* b, const SolverAccepts& a) {
+    // (only DORT builds rough boundaries on the device: every other solver would take the interfaces for flat)
+    if (b->rough_kind || b->rough_params) return "rough_kind / rough_params are read by the DORT solver only: this solver would take the boundaries for flat";
     if (b->emmodel < SMRT_EM_IBA || b->emmodel > SMRT_EM_RAYLEIGH_HOST) return "unknown emmodel";
     if (b->microstructure < SMRT_MS_EXPONENTIAL || b->microstructure > SMRT_MS_TEUBNER_STREY) return "unknown microstructure";
     if (!b->n_layers || !b->thickness || !b->frac_volume || !b->temperature || !b->micro_p1 || !b->frequency || (a.theta && !b->theta))

@@ -50,6 +50,20 @@ class GeometricalOptics:
     """mean_square_slope, or roughness_rms and corr_length (mean_square_slope = 2 | 1 | 3 x (rms / length)^2 for a
     gaussian | exponential | power1.5 autocorrelation); shadow_correction (default True)."""
 
+    device_kind = "geometrical_optics"   # evaluated on the device by DORT (include/smrt_dort.h: SMRT_ROUGH_GEOMETRICAL_OPTICS)
+
+    def device_params(self):
+        """The four numbers of smrt_batch.rough_params: mean square slope, shadow correction."""
+        return (self.mean_square_slope, float(self.shadow_correction), 0.0, 0.0)
+
+    def validity_problems(self, k):
+        """The validity check on arrays of wavenumbers in the incident medium: a boolean array, True where the model is
+        outside its range (k s and k l above 3; never when only the mean square slope is known)."""
+        k = np.asarray(k, float)
+        if self.roughness_rms is None or self.corr_length is None:
+            return np.zeros(k.shape, bool)
+        return (k * self.roughness_rms < 3) | (k * self.corr_length < 3)
+
     args = []
     optional_args = {"mean_square_slope": None, "roughness_rms": None, "corr_length": None, "shadow_correction": True,
                      "autocorrelation_function": "gaussian", "warning_handling": "print"}

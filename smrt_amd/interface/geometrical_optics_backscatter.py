@@ -10,6 +10,11 @@ from .geometrical_optics import GeometricalOptics, shadowing
 
 
 class GeometricalOpticsBackscatter(GeometricalOptics):
+    device_kind = "geometrical_optics_backscatter"   # SMRT_ROUGH_GEOMETRICAL_OPTICS_BACKSCATTER
+
+    def validity_problems(self, k):   # (the lobe is evaluated without the check of the full model)
+        return np.zeros(np.shape(k), bool)
+
     def backscatter(self, eps_1, eps_2, mu_i):
         """[len(mu_i)] sigma0 / (4 pi mu): |R(0)|^2 / (2 s^2 mu^5) exp(-tan^2 / 2 s^2) / (4 pi), shadowed once."""
         mu_i = np.atleast_1d(np.asarray(mu_i, float))

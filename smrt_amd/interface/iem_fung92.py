@@ -38,6 +38,17 @@ class IEM_Fung92(KirchhoffCoherentPart):
     """roughness_rms, corr_length [m]; autocorrelation_function "exponential" (default) or "gaussian"; series_truncation:
     number of terms of the roughness-spectrum series; warning_handling "print" | "nan" | anything else: silent."""
 
+    device_kind = "iem_fung92"   # evaluated on the device by DORT (include/smrt_dort.h: SMRT_ROUGH_IEM_FUNG92)
+
+    def device_params(self):
+        """The four numbers of smrt_batch.rough_params: rms height, correlation length, autocorrelation id, series truncation."""
+        return (self.roughness_rms, self.corr_length, float(self.autocorrelation_function == "gaussian"), float(self.series_truncation))
+
+    def validity_problems(self, k, eps_r):
+        """_outside_validity on arrays: wavenumber in the incident medium and eps_2 / eps_1; True outside the range."""
+        ks, kl = np.abs(np.asarray(k, float) * self.roughness_rms), np.abs(np.asarray(k, float) * self.corr_length)
+        return (ks > 3) | (ks * kl > np.sqrt(np.asarray(eps_r, complex)).real)
+
     args = ["roughness_rms", "corr_length"]
     optional_args = {"autocorrelation_function": "exponential", "warning_handling": "print", "series_truncation": 10}
 

@@ -245,6 +245,7 @@ class DORT(object):
         freq = np.array([float(s.frequency) for s in sensors])
         code = s_code[sens_idx] * len(pack_keys) + p_code[pack_idx]
         sol = _Solution(self, sensors, packs, sens_idx, pack_idx)
+        self.launches = 0
         for g in np.unique(code):
             sel = np.nonzero(code == g)[0]
             u_packs, inv_p = np.unique(pack_idx[sel], return_inverse=True)
@@ -254,8 +255,31 @@ class DORT(object):
             sensor_of = {float(sensors[k].frequency): sensors[k] for k in sens_idx[sel]}
             batch = self._pack(sensor0, [packs[k] for k in u_packs], u_freq, names, sensor_of)
             pairs = inv_f * len(u_packs) + inv_p
-            full = len(pairs) == batch.n_pairs and np.array_equal(pairs, np.arange(batch.n_pairs))
-            out = run_on_devices(batch, self.devices, self.block_threads, pairs=None if full else pairs)
+            out = None
+            for lo, hi in self._rough_parts(batch, len(u_packs)):
+                if (lo, hi) == (0, len(u_packs)):
+                    part, rows, local = batch, slice(None), pairs
+                else:
+                    # the rough matrices of the whole group would exceed the context's workspace budget: a launch per part
+                    # of its snowpacks, the rows gathered into one output
+                    rows = np.nonzero((inv_p >= lo) & (inv_p < hi))[0]
+                    if not len(rows):
+                        continue
+                    part = self._pack(sensor0, [packs[k] for k in u_packs[lo:hi]], u_freq,
+                                      names if isinstance(names, str) else names[lo:hi], sensor_of)
+                    local = inv_f[rows] * (hi - lo) + (inv_p[rows] - lo)
+                full = len(local) == part.n_pairs and np.array_equal(local, np.arange(part.n_pairs))
+                res = run_on_devices(part, self.devices, self.block_threads, pairs=None if full else local)
+                self.launches += 1
+                self._rough_validity(part, res, local, [packs[k] for k in u_packs[lo:hi]])
+                if part is batch:
+                    out = res
+                    break
+                if out is None:
+                    out = BatchOutput(batch, len(pairs))
+                    out.layers[...] = 0.0
+                out.values[rows], out.status[rows], out.streams[rows] = res.values, res.status, res.streams
+                out.layers[rows, :res.layers.shape[1]] = res.layers
             bad = np.nonzero(out.status != 0)[0]
             if len(bad) and self.error_handling == "exception":
                 st = int(out.status[bad[0]])
@@ -351,7 +375,13 @@ class DORT(object):
         mode = sensor0.mode
         substrate = atmosphere = None
         sub0 = sps[0].substrate
-        if sub0 is not None and substrate_kind(sub0, mode) == "host":
+        # rough boundaries the device evaluates itself: a kind and four parameters per boundary travel, no matrix
+        rough = self._rough_on_device(sps, nl, Lmax, mode)
+        if rough is not None and rough[0][0, nl[0]]:
+            eps = batch_permittivities([sp.substrate for sp in sps], freqs)
+            ts = [sp.substrate.temperature if sp.substrate.temperature is not None else 0.0 for sp in sps]
+            substrate = ("flat", eps.real, eps.imag, ts)
+        elif sub0 is not None and substrate_kind(sub0, mode) == "host":
             substrate = self._substrates_on_host(sensor0, sps, freqs, cols, nl, emmodel_names, layer_kind, host,
                                                      scalars=scalars, liquid_water=liquid_water)
         elif sub0 is not None and sub0.device_kind in SOIL_KINDS:
@@ -366,7 +396,7 @@ class DORT(object):
             ts = [sp.substrate.temperature if sp.substrate.temperature is not None else 0.0 for sp in sps]
             substrate = (sub0.device_kind, q[:, :, 0], q[:, :, 1], ts)
         host_interfaces = None
-        if not all(sp.all_interfaces_flat() for sp in sps):
+        if rough is None and not all(sp.all_interfaces_flat() for sp in sps):
             host_interfaces = self._interfaces_on_host(sensor0, sps, freqs, cols, nl, emmodel_names, layer_kind, host,
                                                             scalars=scalars, liquid_water=liquid_water)
         atm0 = sps[0].atmosphere
@@ -384,7 +414,130 @@ class DORT(object):
                            layer_kind=layer_kind, host_emmodel=host,
                            host_scalars=None if scalars is None else scalars[:2],
                            process_coherent_layers=self.process_coherent_layers, host_interfaces=host_interfaces,
-                           liquid_water=liquid_water)
+                           liquid_water=liquid_water, rough=rough)
+
+    # ---- rough boundaries evaluated on the device (include/smrt_dort.h: rough_kind) -----------------------------------------
+    def _rough_on_device(self, sps, nl, Lmax, mode):
+        """(kind [S][Lmax + 1], params [S][Lmax + 1][4]) of smrt_batch.rough_kind / rough_params when the group takes the
+        device route for its rough boundaries: every interface that is not Flat and every substrate evaluated through the
+        protocol has a device kind, and the context advertises the capability.  None: nothing rough, or the host route for
+        the whole group (objects of the reference or of the caller, ReplayInterface, process_coherent_layers, a context
+        without the capability, a solver other than DORT itself)."""
+        from .._native import ROUGH_CODES, ROUGH_M_MAX
+
+        if type(self) is not DORT or self.process_coherent_layers or (mode == "A" and self.m_max > ROUGH_M_MAX):
+            return None
+        # (a group is uniform in substrate_kind: the first substrate answers for it, and a flat group costs nothing more than
+        # the cached all_interfaces_flat of its snowpacks)
+        sub0 = sps[0].substrate
+        if not (sub0 is not None and substrate_kind(sub0, mode) == "host") and all(sp.all_interfaces_flat() for sp in sps):
+            return None
+        kind = np.zeros((len(sps), Lmax + 1), np.int32)
+        params = np.zeros((len(sps), Lmax + 1, 4))
+        subs = [sp.substrate is not None and substrate_kind(sp.substrate, mode) == "host" for sp in sps]
+        if any(subs) and not all(subs):
+            return None
+        for s, sp in enumerate(sps):
+            boundaries = [(i, itf) for i, itf in enumerate(sp.interfaces) if not isinstance(itf, Flat)]
+            if subs[s]:
+                boundaries.append((int(nl[s]), sp.substrate))
+            for i, obj in boundaries:
+                code = ROUGH_CODES.get(getattr(obj, "device_kind", None))
+                if code is None or not callable(getattr(obj, "device_params", None)):
+                    return None
+                kind[s, i], params[s, i] = code, obj.device_params()
+        if not kind.any():
+            return None
+        ctx = get_context((self.devices or [default_device()])[0])
+        if not getattr(ctx, "rough_on_device", False):
+            return None
+        return kind, params
+
+    ROUGH_SMALL_GROUP = 256 << 20   # bytes of rough matrices below which a group is launched whole without asking for the budget
+
+    def _rough_parts(self, batch, n_snowpacks):
+        """[(lo, hi)] ranges of the group's snowpacks, one launch each: one range, unless the batch builds rough matrices on
+        the device and they would exceed the context's workspace budget."""
+        from .._native import rough_matrix_bytes
+
+        kinds = getattr(batch, "rough_kind", None)
+        if kinds is None:
+            return [(0, n_snowpacks)]
+        slots = max(int(np.count_nonzero(kinds[s, :batch.n_layers[s]])) for s in range(n_snowpacks))
+        modes = int(batch.struct.m_max) + 1 if batch.mode == "A" else 1
+        per_snowpack = rough_matrix_bytes(len(batch.frequency), slots, bool(kinds[0, batch.n_layers[0]]), batch.struct.n_max_stream, modes)
+        ctx = get_context((self.devices or [default_device()])[0])
+        # (the budget of a GPU context asks the device for its free memory, which costs more than packing a small group)
+        budget = ctx.__dict__.get("rough_workspace_budget")
+        if budget is None:
+            budget = 0 if per_snowpack * n_snowpacks <= self.ROUGH_SMALL_GROUP else getattr(ctx, "rough_workspace_budget", 0)
+        budget = float(budget or 0)
+        step = n_snowpacks if budget <= 0 else max(1, int(budget // max(per_snowpack, 1)))
+        return [(lo, min(lo + step, n_snowpacks)) for lo in range(0, n_snowpacks, step)]
+
+    def _rough_validity(self, batch, out, pairs, sps):
+        """The validity checks of the rough models of a batch that took the device route, on the host, vectorised over the
+        group: from the effective permittivities the launch returned.  warning_handling "print" warns once per model and
+        cause, "nan" gives the pair NaN results (what the host route's NaN matrices give)."""
+        from .._native import ROUGH_CODES
+
+        kinds = getattr(batch, "rough_kind", None)
+        if kinds is None:
+            return
+        S, Lmax = kinds.shape[0], kinds.shape[1] - 1
+        gp = np.arange(batch.n_pairs) if pairs is None or len(pairs) == 0 else np.asarray(pairs)
+        si, fi = gp % S, gp // S
+        eps = out.layers[:, :, 0] + 1j * out.layers[:, :, 1]            # [rows][Lmax]
+        k0 = 2.0 * np.pi * batch.frequency[fi] / C_SPEED
+        nan_rows = np.zeros(len(gp), bool)
+        # what diffuse_transmission_matrix raises on the host route between layers of identical index; the device gives such
+        # a pair NaN matrices.  (Rows the solve refused, and layers that come back without a permittivity, are not judged.)
+        n_layers = np.asarray(batch.n_layers)
+        for i in range(Lmax):
+            go = (kinds[si, i] == ROUGH_CODES["geometrical_optics"]) & (i < n_layers[si]) & (out.status == 0)
+            if not go.any():
+                continue
+            e1, e2 = eps[go, i], (eps[go, i - 1] if i > 0 else np.ones(int(go.sum()), complex))
+            known = (e1 != 0) & (e2 != 0)
+            ratio = np.sqrt(np.where(known, e1, 1.0)) / np.sqrt(np.where(known, e2, 2.0))
+            same = known & ((np.abs(ratio - 1) < 1e-6) | (np.abs(1 / ratio - 1) < 1e-6))
+            if same.any():
+                n2 = complex(np.sqrt(e1[np.argmax(same)]))
+                raise NotImplementedError(f"the case of successive layers with identical index ({n2:g}) is not implemented")
+        for s, i in zip(*np.nonzero(kinds)):
+            sp = sps[s]
+            obj = sp.substrate if i == batch.n_layers[s] else sp.interfaces[i]
+            handling = getattr(obj, "warning_handling", None)
+            model = getattr(obj, "interface", obj)
+            if handling not in ("print", "nan") or not callable(getattr(model, "validity_problems", None)):
+                continue
+            if model.device_kind != "iem_fung92" and (getattr(model, "roughness_rms", None) is None or getattr(model, "corr_length", None) is None):
+                continue            # (known by its mean square slope alone: the model has no range to leave)
+            rows = np.nonzero(si == s)[0]
+            substrate = i == batch.n_layers[s]
+            if substrate:      # substrate: seen from the last layer
+                sides = [(eps[rows, i - 1], (batch.sub_p1 + 1j * batch.sub_p2)[fi[rows], s])]
+            else:                           # interface: from below and from above (the air above the surface)
+                up = eps[rows, i - 1] if i > 0 else np.ones(len(rows), complex)
+                sides = [(eps[rows, i], up), (up, eps[rows, i])]
+            # (rows the solve refused, and layers it pruned away, come back without a permittivity: nothing to judge there)
+            solved = out.status[rows] == 0
+            bad = np.zeros(len(rows), bool)
+            for e1, e2 in sides:
+                known = solved & (e1 != 0) & (e2 != 0)
+                e1, e2 = np.where(known, e1, 1.0), np.where(known, e2, 2.0)
+                k = k0[rows] * np.sqrt(e1).real
+                bad |= known & (model.validity_problems(k, e2 / e1) if model.device_kind == "iem_fung92" else model.validity_problems(k))
+            if bad.any() and handling == "print":
+                smrt_warn(f"{model.device_kind}: the surface is outside the model's validity range for {int(bad.sum())} of the "
+                          f"{len(rows)} (frequency, snowpack) pairs of this boundary")
+            elif handling == "nan":
+                nan_rows[rows[bad]] = True
+        if nan_rows.any():
+            # (the host route's NaN matrices make the boundary system of such a pair singular: status 4, which
+            # error_handling "exception" raises and "nan" turns into NaN results)
+            out.values[nan_rows] = np.nan
+            out.status[nan_rows] = 4
 
     def _layer_permittivities(self, sps, freqs, cols, nl, emmodel_names, layer_kind, host, scalars=None, liquid_water=None):
         """Effective permittivity of every layer, (F, S, Lmax): from the host-evaluated emmodels if the group has them,

@@ -11,6 +11,15 @@ from ..core.substrate import SOIL_ARGUMENTS, SubstrateBase
 class InterfaceSubstrate(SubstrateBase):
     interface_class = None          # set by the subclasses
 
+    @property
+    def device_kind(self):
+        """The kind DORT evaluates on the device (smrt_batch.rough_kind): the interface model's.  For the grouping of the
+        solvers the substrate stays a "host" object (core/snowpack.py: substrate_kind); DORT decides the route per group."""
+        return getattr(self.interface, "device_kind", None)
+
+    def device_params(self):
+        return self.interface.device_params()
+
     def __init__(self, temperature=None, permittivity_model=None, **interface_parameters):
         soil = {k: interface_parameters.pop(k) for k in SOIL_ARGUMENTS if k in interface_parameters}
         super().__init__(temperature=temperature, permittivity_model=permittivity_model, **soil)
