@@ -15,13 +15,28 @@ using namespace smrt;
 extern "C" __attribute__((visibility("default")))
 const char* smrt_rough_host_refusal(const smrt_batch* b) { return smrt_host::validate(b); }
 
-// Same outputs as smrt_dort_rough_matrices; the caller hands zeroed arrays (slot filled with -1) sized for `slots` slots.
+// Same outputs as smrt_dort_rough_matrices for the pairs of one upload, chosen as smrt_dort_upload / smrt_dort_upload_pairs
+// choose them: the range [pair_begin, pair_begin + pair_count) of the global pairs f * S + s (pair_count < 0: to the end), or
+// the pair_count pairs listed in `pairs` (pair_begin ignored).  The workspace is sized for the pairs of the upload and indexed
+// by the position inside it; the outputs are sized for the whole batch and indexed by the global pair, as rough_prepare lays
+// them out.  The caller hands zeroed arrays (slot filled with -1) sized for `slots` slots: pairs outside the upload stay so.
 // order: the emulator's fiber order (0 forward, 1 reverse, 2 strided).  Returns the number of slots, or -1.
 extern "C" __attribute__((visibility("default")))
-int32_t smrt_rough_host_build(const smrt_batch* b, int32_t order, int32_t* slot, double* itf, double* itf_coh, double* sub, double* sub_coh) {
+int32_t smrt_rough_host_build_pairs(const smrt_batch* b, int32_t order, long long pair_begin, long long pair_count, const long long* pairs,
+                                    int32_t* slot, double* itf, double* itf_coh, double* sub, double* sub_coh) {
     if (smrt_host::validate(b) || !b->rough_kind) return -1;
     const int S = b->n_snowpacks, L = b->n_layers_max, W = L + 1, nmax = b->n_max_stream;
-    const long long np = (long long)S * b->n_frequencies;
+    const long long all = (long long)S * b->n_frequencies;
+    if (pairs) {
+        pair_begin = 0;
+        if (pair_count <= 0) return -1;
+        for (long long i = 0; i < pair_count; ++i)
+            if (pairs[i] < 0 || pairs[i] >= all) return -1;
+    } else {
+        if (pair_count < 0) pair_count = all - pair_begin;
+        if (pair_begin < 0 || pair_count <= 0 || pair_begin + pair_count > all) return -1;
+    }
+    const long long np = pair_count;
     int slots = 0;
     for (int s = 0; s < S; ++s) {
         int c = 0;
@@ -45,7 +60,7 @@ int32_t smrt_rough_host_build(const smrt_batch* b, int32_t order, int32_t* slot,
     r.S = S; r.Lmax = L; r.F = b->n_frequencies; r.nmax = nmax; r.active = b->mode == SMRT_MODE_ACTIVE ? 1 : 0;
     r.nmodes = r.active ? b->m_max + 1 : 1;
     r.emmodel = b->emmodel; r.micro = b->microstructure;
-    r.pair_begin = 0; r.pair_count = np; r.pair_map = nullptr;
+    r.pair_begin = pair_begin; r.pair_count = np; r.pair_map = pairs;
     r.n_layers = nl.data(); r.frac_volume = b->frac_volume; r.temperature = b->temperature; r.p1 = b->micro_p1;
     r.p2 = b->micro_p2 ? b->micro_p2 : b->micro_p1; r.frequency = b->frequency;
     r.layer_kind = b->layer_kind ? kinds.data() : nullptr; r.liquid_water = b->liquid_water; r.host_layer = b->host_layer;
@@ -72,4 +87,10 @@ int32_t smrt_rough_host_build(const smrt_batch* b, int32_t order, int32_t* slot,
     for (long long blk = 0; blk < tasks * 2 * nmax; ++blk)
         emu::run_block(kRoughNT, order, [&]() { rough_hemi_block(r, blk, lds.data()); });
     return slots;
+}
+
+// every pair of the batch
+extern "C" __attribute__((visibility("default")))
+int32_t smrt_rough_host_build(const smrt_batch* b, int32_t order, int32_t* slot, double* itf, double* itf_coh, double* sub, double* sub_coh) {
+    return smrt_rough_host_build_pairs(b, order, 0, -1, nullptr, slot, itf, itf_coh, sub, sub_coh);
 }
