@@ -7,7 +7,7 @@
 #include <cstring>
 #include <string>
 
-#include "first_order_kernel.hpp"
+#include "solver_describe.hpp"
 #include "solver_host.hpp"
 #include "solver_refusals.hpp"
 
@@ -65,33 +65,24 @@ int32_t smrt_first_order_upload_pairs(smrt_dort_ctx* ctx, const smrt_batch* b, c
     if (!ctx->first_order) ctx->first_order = new FirstOrderState();
     FirstOrderState* st = ctx->first_order;
     st->uploaded = false;
-    const size_t S = b->n_snowpacks, L = b->n_layers_max, F = b->n_frequencies, T = b->n_theta, N = (size_t)n_pairs;
-    const size_t FS = F * S;
-    FoBatch d{};
-    d.S = (int)S; d.Lmax = (int)L; d.F = (int)F; d.n_theta = (int)T;
-    d.emmodel = b->emmodel; d.micro = b->microstructure; d.sub_kind = b->substrate_kind;
-    d.n_pairs = n_pairs;
+    FoBatch d = solver_describe::first_order(b, x, n_pairs);
+    const solver_describe::FoExtents n = solver_describe::extents(d);
     using solver_host::upload;
     if (solver_host::upload_batch(ctx, st, b, pairs, d)) return -1;
-    if (upload(ctx, st->theta, b->theta, T * sizeof(double), d.theta)) return -1;
-    if (b->host_layer && upload(ctx, st->hostlayer, b->host_layer, FS * L * 4 * sizeof(double), d.host_layer)) return -1;
-    if (b->host_iba_coeff && upload(ctx, st->hostcoeff, b->host_iba_coeff, FS * L * sizeof(double), d.host_coeff)) return -1;
+    if (upload(ctx, st->theta, b->theta, n.theta * sizeof(double), d.theta)) return -1;
+    if (b->host_layer && upload(ctx, st->hostlayer, b->host_layer, n.host_layer * sizeof(double), d.host_layer)) return -1;
+    if (b->host_iba_coeff && upload(ctx, st->hostcoeff, b->host_iba_coeff, n.host_coeff * sizeof(double), d.host_coeff)) return -1;
     if (x && x->host_interface_slot) {
-        d.n_slots = x->n_interface_slots;
-        if (upload(ctx, st->slot, x->host_interface_slot, FS * (L + 1) * sizeof(int32_t), d.itf_slot) ||
-            upload(ctx, st->values, x->host_interface_values, FS * (size_t)d.n_slots * T * kFoInterfaceDoubles * sizeof(double), d.itf_values))
+        if (upload(ctx, st->slot, x->host_interface_slot, n.itf_slot * sizeof(int32_t), d.itf_slot) ||
+            upload(ctx, st->values, x->host_interface_values, n.itf_values * sizeof(double), d.itf_values))
             return -1;
     }
-    if (x && x->host_phase_samples && upload(ctx, st->phase, x->host_phase_samples, FS * L * T * 16 * sizeof(double), d.host_phase)) return -1;
-    HIPCHK(st->stage.reserve((size_t)FO_ROWS * L * N * sizeof(double)));
-    HIPCHK(st->out.reserve(N * 16 * T * sizeof(double)));
-    HIPCHK(st->status.reserve(N * sizeof(int32_t)));
-    HIPCHK(st->layer.reserve(N * L * 5 * sizeof(double)));
-    HIPCHK(st->lb.reserve(N * (L + 1) * T * 4 * sizeof(double)));
-    HIPCHK(st->diag.reserve(N * 2 * sizeof(double)));
-    d.stage = (double*)st->stage.p; d.out = (double*)st->out.p; d.status = (int*)st->status.p;
-    d.layer_out = (double*)st->layer.p; d.layer_backscatter = (double*)st->lb.p; d.diag = (double*)st->diag.p;
-    if (solver_host::uploads_done(ctx)) return -1;
+    if (x && x->host_phase_samples && upload(ctx, st->phase, x->host_phase_samples, n.host_phase * sizeof(double), d.host_phase)) return -1;
+    using solver_host::reserve;
+    if (reserve(ctx, st->stage, n.stage, d.stage) || reserve(ctx, st->out, n.out, d.out) || reserve(ctx, st->status, n.status, d.status) ||
+        reserve(ctx, st->layer, n.layer_out, d.layer_out) || reserve(ctx, st->lb, n.layer_backscatter, d.layer_backscatter) ||
+        reserve(ctx, st->diag, n.diag, d.diag) || solver_host::uploads_done(ctx))
+        return -1;
     st->dev = d;
     st->uploaded = true;
     st->timed = false;
@@ -137,13 +128,13 @@ int32_t smrt_first_order_download(smrt_dort_ctx* ctx, double* out, int32_t* stat
     if (!st || !st->uploaded) { ctx->err = "no first-order batch uploaded"; return -1; }
     HIPCHK(hipSetDevice(ctx->device));
     const FoBatch& d = st->dev;
-    const size_t N = (size_t)d.n_pairs, L = d.Lmax, T = d.n_theta;
-    if (out) HIPCHK(hipMemcpyAsync(out, d.out, N * 16 * T * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-    if (status) HIPCHK(hipMemcpyAsync(status, d.status, N * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
-    if (layer_out) HIPCHK(hipMemcpyAsync(layer_out, d.layer_out, N * L * 5 * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    const solver_describe::FoExtents n = solver_describe::extents(d);
+    if (out) HIPCHK(hipMemcpyAsync(out, d.out, n.out * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    if (status) HIPCHK(hipMemcpyAsync(status, d.status, n.status * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
+    if (layer_out) HIPCHK(hipMemcpyAsync(layer_out, d.layer_out, n.layer_out * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
     if (backscatter_layer)
-        HIPCHK(hipMemcpyAsync(backscatter_layer, d.layer_backscatter, N * (L + 1) * T * 4 * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-    if (diag) HIPCHK(hipMemcpyAsync(diag, d.diag, N * 2 * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+        HIPCHK(hipMemcpyAsync(backscatter_layer, d.layer_backscatter, n.layer_backscatter * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    if (diag) HIPCHK(hipMemcpyAsync(diag, d.diag, n.diag * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
     HIPCHK(hipStreamSynchronize(ctx->stream));
     return 0;
 }

@@ -7,7 +7,7 @@
 #include <cstddef>
 #include <string>
 
-#include "multifresnel_kernel.hpp"
+#include "solver_describe.hpp"
 #include "solver_host.hpp"
 #include "solver_refusals.hpp"
 
@@ -53,26 +53,16 @@ int32_t smrt_multifresnel_upload_pairs(smrt_dort_ctx* ctx, const smrt_batch* b, 
     if (!ctx->multifresnel) ctx->multifresnel = new MultiFresnelState();
     MultiFresnelState* st = ctx->multifresnel;
     st->uploaded = false;
-    const size_t S = b->n_snowpacks, L = b->n_layers_max, F = b->n_frequencies, T = b->n_theta, N = (size_t)n_pairs;
-    MfBatch d{};
-    d.S = (int)S; d.Lmax = (int)L; d.F = (int)F; d.n_theta = (int)T;
-    d.emmodel = b->emmodel; d.micro = b->microstructure; d.sub_kind = b->substrate_kind;
-    d.prune = prune_none ? INFINITY : prune_deep_snowpack;
-    d.steepest = 0;
-    for (size_t t = 1; t < T; ++t) if (mu[t] > mu[d.steepest]) d.steepest = (int)t;
-    d.n_pairs = n_pairs;
+    MfBatch d = solver_describe::multifresnel(b, mu, prune_deep_snowpack, prune_none, n_pairs);
+    const solver_describe::MfExtents n = solver_describe::extents(d);
     if (solver_host::upload_batch(ctx, st, b, pairs, d)) return -1;
-    if (solver_host::upload(ctx, st->mu, mu, T * sizeof(double), d.mu)) return -1;
-    if (b->substrate_kind == SMRT_SUBSTRATE_FLAT && solver_host::upload(ctx, st->subT, b->substrate_temperature, S * sizeof(double), d.sub_T)) return -1;
-    HIPCHK(st->stage.reserve((size_t)MF_ROWS * (L + 1) * N * sizeof(double)));
-    HIPCHK(st->out.reserve(N * 2 * T * sizeof(double)));
-    HIPCHK(st->status.reserve(N * T * sizeof(int32_t)));
-    HIPCHK(st->used.reserve(N * sizeof(int32_t)));
-    HIPCHK(st->tau.reserve(N * sizeof(double)));
-    HIPCHK(st->layer.reserve(N * L * 5 * sizeof(double)));
-    d.stage = (double*)st->stage.p; d.out = (double*)st->out.p; d.status = (int*)st->status.p;
-    d.layers_used = (int*)st->used.p; d.tau_snowpack = (double*)st->tau.p; d.layer_out = (double*)st->layer.p;
-    if (solver_host::uploads_done(ctx)) return -1;
+    if (solver_host::upload(ctx, st->mu, mu, n.mu * sizeof(double), d.mu)) return -1;
+    if (b->substrate_kind == SMRT_SUBSTRATE_FLAT && solver_host::upload(ctx, st->subT, b->substrate_temperature, n.sub_T * sizeof(double), d.sub_T)) return -1;
+    using solver_host::reserve;
+    if (reserve(ctx, st->stage, n.stage, d.stage) || reserve(ctx, st->out, n.out, d.out) || reserve(ctx, st->status, n.status, d.status) ||
+        reserve(ctx, st->used, n.layers_used, d.layers_used) || reserve(ctx, st->tau, n.tau_snowpack, d.tau_snowpack) ||
+        reserve(ctx, st->layer, n.layer_out, d.layer_out) || solver_host::uploads_done(ctx))
+        return -1;
     st->dev = d;
     st->uploaded = true;
     st->timed = false;
@@ -118,12 +108,12 @@ int32_t smrt_multifresnel_download(smrt_dort_ctx* ctx, double* out, int32_t* sta
     if (!st || !st->uploaded) { ctx->err = "no multi-Fresnel batch uploaded"; return -1; }
     HIPCHK(hipSetDevice(ctx->device));
     const MfBatch& d = st->dev;
-    const size_t N = (size_t)d.n_pairs, L = d.Lmax, T = d.n_theta;
-    if (out) HIPCHK(hipMemcpyAsync(out, d.out, N * 2 * T * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-    if (status) HIPCHK(hipMemcpyAsync(status, d.status, N * T * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
-    if (layers_used) HIPCHK(hipMemcpyAsync(layers_used, d.layers_used, N * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
-    if (tau_snowpack) HIPCHK(hipMemcpyAsync(tau_snowpack, d.tau_snowpack, N * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-    if (layer_out) HIPCHK(hipMemcpyAsync(layer_out, d.layer_out, N * L * 5 * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    const solver_describe::MfExtents n = solver_describe::extents(d);
+    if (out) HIPCHK(hipMemcpyAsync(out, d.out, n.out * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    if (status) HIPCHK(hipMemcpyAsync(status, d.status, n.status * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
+    if (layers_used) HIPCHK(hipMemcpyAsync(layers_used, d.layers_used, n.layers_used * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
+    if (tau_snowpack) HIPCHK(hipMemcpyAsync(tau_snowpack, d.tau_snowpack, n.tau_snowpack * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    if (layer_out) HIPCHK(hipMemcpyAsync(layer_out, d.layer_out, n.layer_out * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
     HIPCHK(hipStreamSynchronize(ctx->stream));
     return 0;
 }

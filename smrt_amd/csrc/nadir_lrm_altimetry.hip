@@ -7,7 +7,7 @@
 #include <cstddef>
 #include <string>
 
-#include "nadir_lrm_altimetry_kernel.hpp"
+#include "solver_describe.hpp"
 #include "solver_host.hpp"
 #include "solver_refusals.hpp"
 
@@ -47,14 +47,11 @@ namespace smrt_launch {
 void lrm_release(smrt_dort_ctx* ctx) { solver_host::release(ctx->lrm); }
 }  // namespace smrt_launch
 
-static int lrm_rows(const smrt_lrm_params* p) { return p->n_mu > 1 ? 2 * p->n_mu + 1 : p->return_contributions ? 3 : 1; }
-static int lrm_out_rows(const smrt_lrm_params* p) { return p->return_contributions ? 3 : p->skip_pfs_convolution ? lrm_rows(p) : 1; }
-
 extern "C" {
 
 int32_t smrt_lrm_out_stride(const smrt_lrm_params* p) {
     if (!p || p->ngate < 1 || p->oversampling < 1 || p->n_mu < 1) return -1;
-    return lrm_out_rows(p) * (p->return_oversampled ? p->ngate * p->oversampling : p->ngate);
+    return solver_describe::lrm_out_rows(p) * (p->return_oversampled ? p->ngate * p->oversampling : p->ngate);
 }
 
 int32_t smrt_lrm_abi(int32_t* out, int32_t capacity) {
@@ -77,41 +74,25 @@ int32_t smrt_lrm_upload_pairs(smrt_dort_ctx* ctx, const smrt_batch* b, const smr
     if (!ctx->lrm) ctx->lrm = new LrmState();
     LrmState* st = ctx->lrm;
     st->uploaded = false;
-    const size_t S = b->n_snowpacks, L = b->n_layers_max, F = b->n_frequencies, NP = (size_t)n_pairs;
-    const size_t FSL = F * S * L;
-    LrmBatch d{};
+    LrmBatch d = solver_describe::nadir_lrm_altimetry(b, p, n_pairs);
     FoBatch& fo = d.fo;
-    fo.S = (int)S; fo.Lmax = (int)L; fo.F = (int)F; fo.n_theta = 1;
-    fo.emmodel = b->emmodel; fo.micro = b->microstructure; fo.sub_kind = 0; fo.n_slots = 0;
-    fo.n_pairs = n_pairs;
-    d.ngate = p->ngate; d.os = p->oversampling; d.n_mu = p->n_mu; d.shift = p->shift;
-    d.contributions = p->return_contributions ? 1 : 0; d.oversampled = p->return_oversampled ? 1 : 0;
-    d.skip_pfs = p->skip_pfs_convolution ? 1 : 0;
-    d.N = p->ngate * p->oversampling;
-    d.rows = lrm_rows(p); d.out_rows = lrm_out_rows(p); d.n_out = d.oversampled ? d.N : d.ngate;
-    d.altitude = p->altitude; d.bandwidth = p->pulse_bandwidth; d.gain = p->antenna_gain; d.gamma = p->gamma;
-    d.off_nadir = p->off_nadir_angle; d.nominal_gate = p->nominal_gate; d.pulse_sigma = p->pulse_sigma;
+    const solver_describe::LrmExtents n = solver_describe::extents(d);
+    const solver_describe::FoExtents nf = solver_describe::extents(fo);
     using solver_host::upload;
     if (solver_host::upload_batch(ctx, st, b, pairs, fo)) return -1;   // (fo.sub_kind is none: the substrate is not read)
-    if (b->host_layer && upload(ctx, st->hostlayer, b->host_layer, FSL * 4 * sizeof(double), fo.host_layer)) return -1;
-    if (b->host_iba_coeff && upload(ctx, st->hostcoeff, b->host_iba_coeff, FSL * sizeof(double), fo.host_coeff)) return -1;
-    if (p->n_mu > 1 && upload(ctx, st->tinc, p->t_inc, p->n_mu * sizeof(double), d.t_inc)) return -1;
-    if (p->sigma_surface && upload(ctx, st->sigma, p->sigma_surface, S * sizeof(double), d.sigma_surface)) return -1;
-    if (p->surface_slope && upload(ctx, st->slope, p->surface_slope, S * sizeof(double), d.surface_slope)) return -1;
-    if (p->interface_values && upload(ctx, st->itf, p->interface_values, F * S * (L + 1) * (1 + p->n_mu) * sizeof(double), d.itf)) return -1;
-    HIPCHK(st->stage.reserve((size_t)FO_ROWS * L * NP * sizeof(double)));
-    HIPCHK(st->bs.reserve(L * NP * sizeof(double)));
-    HIPCHK(st->prefix.reserve(NP * LRM_PREFIX_ROWS * (L + 1) * sizeof(double)));
-    HIPCHK(st->vsd.reserve(NP * d.rows * d.N * sizeof(double)));
-    HIPCHK(st->out.reserve(NP * d.out_rows * d.n_out * sizeof(double)));
-    HIPCHK(st->zgate.reserve(NP * d.n_out * sizeof(double)));
-    HIPCHK(st->status.reserve(NP * sizeof(int32_t)));
-    HIPCHK(st->layer.reserve(NP * L * 5 * sizeof(double)));
-    fo.stage = (double*)st->stage.p; fo.layer_out = (double*)st->layer.p;
-    d.bs = (double*)st->bs.p; d.prefix = (double*)st->prefix.p; d.vsd = (double*)st->vsd.p; d.out = (double*)st->out.p;
-    d.z_gate = (double*)st->zgate.p; d.status = (int*)st->status.p;
-    st->lds_vertical = lrm_vertical_lds_bytes(d.N, (int)L);
-    st->lds_waveform = lrm_waveform_lds_bytes(d.N, d.n_mu);
+    if (b->host_layer && upload(ctx, st->hostlayer, b->host_layer, nf.host_layer * sizeof(double), fo.host_layer)) return -1;
+    if (b->host_iba_coeff && upload(ctx, st->hostcoeff, b->host_iba_coeff, nf.host_coeff * sizeof(double), fo.host_coeff)) return -1;
+    if (p->n_mu > 1 && upload(ctx, st->tinc, p->t_inc, n.t_inc * sizeof(double), d.t_inc)) return -1;
+    if (p->sigma_surface && upload(ctx, st->sigma, p->sigma_surface, n.per_snowpack * sizeof(double), d.sigma_surface)) return -1;
+    if (p->surface_slope && upload(ctx, st->slope, p->surface_slope, n.per_snowpack * sizeof(double), d.surface_slope)) return -1;
+    if (p->interface_values && upload(ctx, st->itf, p->interface_values, n.itf * sizeof(double), d.itf)) return -1;
+    using solver_host::reserve;
+    if (reserve(ctx, st->stage, n.stage, fo.stage) || reserve(ctx, st->bs, n.bs, d.bs) || reserve(ctx, st->prefix, n.prefix, d.prefix) ||
+        reserve(ctx, st->vsd, n.vsd, d.vsd) || reserve(ctx, st->out, n.out, d.out) || reserve(ctx, st->zgate, n.z_gate, d.z_gate) ||
+        reserve(ctx, st->status, n.status, d.status) || reserve(ctx, st->layer, n.layer_out, fo.layer_out))
+        return -1;
+    st->lds_vertical = n.lds_vertical;
+    st->lds_waveform = n.lds_waveform;
     if (solver_host::uploads_done(ctx)) return -1;
     st->dev = d;
     st->uploaded = true;
@@ -153,7 +134,7 @@ int32_t smrt_lrm_layers(smrt_dort_ctx* ctx, double* layer_out) {
     const long long items = d.fo.n_pairs * d.fo.Lmax;
     hipLaunchKernelGGL(lrm_layers_kernel, dim3((unsigned)((items + kLrmThreads - 1) / kLrmThreads)), dim3(kLrmThreads), 0, ctx->stream, d);
     HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(layer_out, d.fo.layer_out, (size_t)items * 5 * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(hipMemcpyAsync(layer_out, d.fo.layer_out, solver_describe::extents(d).layer_out * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
     HIPCHK(hipStreamSynchronize(ctx->stream));
     return 0;
 }
@@ -178,12 +159,12 @@ int32_t smrt_lrm_download(smrt_dort_ctx* ctx, double* out, int32_t* status, doub
     if (!st || !st->uploaded) { ctx->err = "no altimetry batch uploaded"; return -1; }
     HIPCHK(hipSetDevice(ctx->device));
     const LrmBatch& d = st->dev;
-    const size_t NP = (size_t)d.fo.n_pairs, L = d.fo.Lmax;
-    if (out) HIPCHK(hipMemcpyAsync(out, d.out, NP * d.out_rows * d.n_out * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-    if (status) HIPCHK(hipMemcpyAsync(status, d.status, NP * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
-    if (z_gate) HIPCHK(hipMemcpyAsync(z_gate, d.z_gate, NP * d.n_out * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-    if (layer_out) HIPCHK(hipMemcpyAsync(layer_out, d.fo.layer_out, NP * L * 5 * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-    if (vertical) HIPCHK(hipMemcpyAsync(vertical, d.vsd, NP * d.rows * d.N * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    const solver_describe::LrmExtents n = solver_describe::extents(d);
+    if (out) HIPCHK(hipMemcpyAsync(out, d.out, n.out * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    if (status) HIPCHK(hipMemcpyAsync(status, d.status, n.status * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
+    if (z_gate) HIPCHK(hipMemcpyAsync(z_gate, d.z_gate, n.z_gate * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    if (layer_out) HIPCHK(hipMemcpyAsync(layer_out, d.fo.layer_out, n.layer_out * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    if (vertical) HIPCHK(hipMemcpyAsync(vertical, d.vsd, n.vsd * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
     HIPCHK(hipStreamSynchronize(ctx->stream));
     return 0;
 }

@@ -9,7 +9,7 @@
 #include <cstddef>
 #include <string>
 
-#include "nadir_sar_altimetry_kernel.hpp"
+#include "solver_describe.hpp"
 #include "solver_host.hpp"
 #include "solver_refusals.hpp"
 
@@ -100,7 +100,7 @@ int32_t smrt_sar_upload_pairs(smrt_dort_ctx* ctx, const smrt_batch* b, const smr
     const char* why = solver_refusals::nadir_sar_altimetry(b, p);
     if (why) { ctx->err = why; return -1; }
     if (solver_host::check_pairs(ctx, pairs, &n_pairs, (int64_t)b->n_snowpacks)) return -1;
-    const size_t S = b->n_snowpacks, L = b->n_layers_max, NP = (size_t)n_pairs;
+    const size_t NP = (size_t)n_pairs;
     const size_t stride = (size_t)smrt_sar_out_stride(p);
     if (NP * stride * sizeof(double) > solver_refusals::kSarOutputBudget) {
         ctx->err = "the maps of these pairs do not fit the output budget of the nadir SAR altimetry solver: launch fewer pairs at a time";
@@ -110,58 +110,32 @@ int32_t smrt_sar_upload_pairs(smrt_dort_ctx* ctx, const smrt_batch* b, const smr
     if (!ctx->sar) ctx->sar = new SarState();
     SarState* st = ctx->sar;
     st->uploaded = false;
-    const size_t SL = S * L;
-    SarBatch d{};
+    SarBatch d = solver_describe::nadir_sar_altimetry(b, p, n_pairs);
     LrmBatch& lb = d.lrm;
     FoBatch& fo = lb.fo;
-    fo.S = (int)S; fo.Lmax = (int)L; fo.F = 1; fo.n_theta = 1;
-    fo.emmodel = b->emmodel; fo.micro = b->microstructure; fo.sub_kind = 0; fo.n_slots = 0;
-    fo.n_pairs = n_pairs;
-    lb.ngate = p->ngate; lb.os = p->oversampling_time; lb.n_mu = 1; lb.shift = 0;
-    lb.contributions = 0; lb.oversampled = p->return_oversampled ? 1 : 0; lb.skip_pfs = 0;
-    lb.N = p->ngate * p->oversampling_time;
-    lb.rows = 1; lb.out_rows = 1; lb.n_out = lb.oversampled ? lb.N : lb.ngate; lb.sar = 1;
-    lb.altitude = p->altitude; lb.bandwidth = p->pulse_bandwidth; lb.nominal_gate = p->nominal_gate;
-    d.ndoppler = p->ndoppler; d.osd = p->oversampling_doppler; d.ND = p->ndoppler * p->oversampling_doppler;
-    d.out_rows = p->n_rows; d.n_tab = p->n_tables;
-    d.n_t = lb.n_out; d.n_d = lb.oversampled ? d.ND : d.ndoppler;
-    d.prf = p->pulse_repetition_frequency; d.wavelength = p->wavelength; d.velocity = p->velocity; d.alpha = p->alpha;
-    d.pitch = p->pitch_angle; d.roll = p->roll_angle; d.sigma_p = p->sigma_p; d.theta_lim = p->theta_lim;
-    d.gamma_x = p->gamma_x; d.gamma_y = p->gamma_y; d.l_gamma = p->l_gamma; d.lz = p->lz; d.pu = p->pu; d.nu_coherent = p->nu_coherent;
-    const bool h14 = p->delay_doppler_model == SMRT_SAR_HALIMI14;
-    if (h14) sar_h14_setup(d, p->slant_range_correction ? 1 : 0, p->delay_window_widening, p->h14_pu, p->h14_gamma, p->burst_duration);
+    const solver_describe::SarExtents n = solver_describe::extents(d);
+    const solver_describe::FoExtents nf = solver_describe::extents(fo);
     using solver_host::upload;
     if (solver_host::upload_batch(ctx, st, b, pairs, fo)) return -1;   // (fo.sub_kind is none: the substrate is not read)
-    if (b->host_layer && upload(ctx, st->hostlayer, b->host_layer, SL * 4 * sizeof(double), fo.host_layer)) return -1;
-    if (b->host_iba_coeff && upload(ctx, st->hostcoeff, b->host_iba_coeff, SL * sizeof(double), fo.host_coeff)) return -1;
-    if (upload(ctx, st->tabsigma, p->table_sigma, p->n_tables * sizeof(double), d.tab_sigma)) return -1;
-    if (upload(ctx, st->tabindex, p->table_index, S * sizeof(int32_t), d.tab_index)) return -1;
-    if (upload(ctx, st->bv, p->boundary_values, S * (L + 1) * SAR_BV * sizeof(double), lb.itf)) return -1;
-    if (upload(ctx, st->rowmap, p->row_map, S * (2 * (L + 1) + 2) * sizeof(int32_t), d.row_map)) return -1;
-    HIPCHK(st->stage.reserve((size_t)FO_ROWS * L * NP * sizeof(double)));
-    HIPCHK(st->bs.reserve(L * NP * sizeof(double)));
-    HIPCHK(st->prefix.reserve(NP * LRM_PREFIX_ROWS * (L + 1) * sizeof(double)));
-    HIPCHK(st->vsd.reserve(NP * lb.N * sizeof(double)));
-    HIPCHK(st->zgate.reserve(NP * lb.n_out * sizeof(double)));
-    HIPCHK(st->status.reserve(NP * sizeof(int32_t)));
-    HIPCHK(st->layer.reserve(NP * L * 5 * sizeof(double)));
-    HIPCHK(st->tables.reserve((size_t)p->n_tables * (h14 ? 1 : 2) * lb.N * d.ND * sizeof(double)));
-    if (h14) {
-        HIPCHK(st->h14doppler.reserve((size_t)d.ND * d.N_wide * sizeof(double)));
-        HIPCHK(st->h14kernel.reserve((size_t)p->n_tables * d.M * sizeof(double)));
-        d.h14_doppler = (double*)st->h14doppler.p; d.h14_kernel = (double*)st->h14kernel.p;
-    }
-    HIPCHK(st->echo.reserve(NP * (L + 1) * SAR_ECHO * sizeof(double)));
-    HIPCHK(st->out.reserve(NP * stride * sizeof(double)));
-    fo.stage = (double*)st->stage.p; fo.layer_out = (double*)st->layer.p;
-    lb.bs = (double*)st->bs.p; lb.prefix = (double*)st->prefix.p; lb.vsd = (double*)st->vsd.p; lb.out = nullptr;
-    lb.z_gate = (double*)st->zgate.p; lb.status = (int*)st->status.p;
-    d.tables = (double*)st->tables.p; d.echo = (double*)st->echo.p; d.out = (double*)st->out.p;
-    st->lds_vertical = lrm_vertical_lds_bytes(lb.N, (int)L);
-    st->lds_combine = h14 ? sar_h14_combine_lds_bytes(lb.N, d.osd) : sar_combine_lds_bytes(lb.N, d.osd);
-    st->lds_h14_doppler = sar_h14_doppler_lds_bytes(d.ND);
-    st->lds_h14_kernel = h14 ? sar_h14_kernel_lds_bytes(d.M) : 0;
-    st->lds_h14_delay = h14 ? sar_h14_delay_lds_bytes(d.N_wide, d.M) : 0;
+    if (b->host_layer && upload(ctx, st->hostlayer, b->host_layer, nf.host_layer * sizeof(double), fo.host_layer)) return -1;
+    if (b->host_iba_coeff && upload(ctx, st->hostcoeff, b->host_iba_coeff, nf.host_coeff * sizeof(double), fo.host_coeff)) return -1;
+    if (upload(ctx, st->tabsigma, p->table_sigma, n.tab_sigma * sizeof(double), d.tab_sigma)) return -1;
+    if (upload(ctx, st->tabindex, p->table_index, n.tab_index * sizeof(int32_t), d.tab_index)) return -1;
+    if (upload(ctx, st->bv, p->boundary_values, n.boundary_values * sizeof(double), lb.itf)) return -1;
+    if (upload(ctx, st->rowmap, p->row_map, n.row_map * sizeof(int32_t), d.row_map)) return -1;
+    using solver_host::reserve;
+    if (reserve(ctx, st->stage, n.lrm.stage, fo.stage) || reserve(ctx, st->bs, n.lrm.bs, lb.bs) || reserve(ctx, st->prefix, n.lrm.prefix, lb.prefix) ||
+        reserve(ctx, st->vsd, n.lrm.vsd, lb.vsd) || reserve(ctx, st->zgate, n.lrm.z_gate, lb.z_gate) || reserve(ctx, st->status, n.lrm.status, lb.status) ||
+        reserve(ctx, st->layer, n.lrm.layer_out, fo.layer_out) || reserve(ctx, st->tables, n.tables, d.tables))
+        return -1;
+    if (d.model == kSarHalimi14 && (reserve(ctx, st->h14doppler, n.h14_doppler, d.h14_doppler) || reserve(ctx, st->h14kernel, n.h14_kernel, d.h14_kernel)))
+        return -1;
+    if (reserve(ctx, st->echo, n.echo, d.echo) || reserve(ctx, st->out, n.out, d.out)) return -1;
+    st->lds_vertical = n.lrm.lds_vertical;
+    st->lds_combine = n.lds_combine;
+    st->lds_h14_doppler = n.lds_h14_doppler;
+    st->lds_h14_kernel = n.lds_h14_kernel;
+    st->lds_h14_delay = n.lds_h14_delay;
     if (solver_host::uploads_done(ctx)) return -1;
     st->dev = d;
     st->uploaded = true;
@@ -235,13 +209,13 @@ int32_t smrt_sar_download(smrt_dort_ctx* ctx, double* out, int32_t* status, doub
     if (!st || !st->uploaded) { ctx->err = "no SAR altimetry batch uploaded"; return -1; }
     HIPCHK(hipSetDevice(ctx->device));
     const SarBatch& d = st->dev;
-    const size_t NP = (size_t)d.lrm.fo.n_pairs, L = d.lrm.fo.Lmax;
-    if (out) HIPCHK(hipMemcpyAsync(out, d.out, NP * d.out_rows * d.n_t * d.n_d * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-    if (status) HIPCHK(hipMemcpyAsync(status, d.lrm.status, NP * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
-    if (z_gate) HIPCHK(hipMemcpyAsync(z_gate, d.lrm.z_gate, NP * d.lrm.n_out * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-    if (layer_out) HIPCHK(hipMemcpyAsync(layer_out, d.lrm.fo.layer_out, NP * L * 5 * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-    if (vertical) HIPCHK(hipMemcpyAsync(vertical, d.lrm.vsd, NP * d.lrm.N * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-    if (echo) HIPCHK(hipMemcpyAsync(echo, d.echo, NP * (L + 1) * SAR_ECHO * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    const solver_describe::SarExtents n = solver_describe::extents(d);
+    if (out) HIPCHK(hipMemcpyAsync(out, d.out, n.out * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    if (status) HIPCHK(hipMemcpyAsync(status, d.lrm.status, n.lrm.status * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
+    if (z_gate) HIPCHK(hipMemcpyAsync(z_gate, d.lrm.z_gate, n.lrm.z_gate * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    if (layer_out) HIPCHK(hipMemcpyAsync(layer_out, d.lrm.fo.layer_out, n.lrm.layer_out * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    if (vertical) HIPCHK(hipMemcpyAsync(vertical, d.lrm.vsd, n.lrm.vsd * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    if (echo) HIPCHK(hipMemcpyAsync(echo, d.echo, n.echo * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
     HIPCHK(hipStreamSynchronize(ctx->stream));
     return 0;
 }

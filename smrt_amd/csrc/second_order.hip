@@ -10,7 +10,7 @@
 #include <string>
 #include <vector>
 
-#include "second_order_kernel.hpp"
+#include "solver_describe.hpp"
 #include "solver_host.hpp"
 #include "solver_refusals.hpp"
 
@@ -94,16 +94,13 @@ int32_t smrt_second_order_upload_pairs(smrt_dort_ctx* ctx, const smrt_batch* b, 
     SecondOrderState* st = ctx->second_order;
     FoBatch* fo = smrt_launch::first_order_resident(ctx);
     if (!fo) { ctx->err = "no first-order batch resident"; return -1; }
-    const size_t N = (size_t)fo->n_pairs, L = b->n_layers_max, T = b->n_theta, NM = b->n_max_stream, MM = b->m_max;
-    const size_t FS = (size_t)b->n_frequencies * b->n_snowpacks;
-    So2Batch d{};
-    d.nmax = (int)NM; d.m_max = (int)MM; d.nsamp = azimuth_samples(b->m_max);
-    d.interlayer = (x && x->compute_scattering_interlayer) ? 1 : 0;
+    So2Batch d = solver_describe::second_order(b, x, fo->n_pairs);
+    const size_t N = (size_t)fo->n_pairs, NM = d.nmax, carry_doubles = solver_describe::extents(*fo).carry;
+    const solver_describe::So2Extents row = solver_describe::extents(d, 1);
     const int64_t budget = (x && x->workspace_budget_bytes > 0) ? x->workspace_budget_bytes : kSo2DefaultBudget;
-    const size_t sub_bytes = (x && x->substrate_diffuse_modes) ? FS * L * T * NM * MM * kSo2SubDoubles * sizeof(double) : 0;
-    const size_t fixed = NM * 8 + sub_bytes + N * L * T * kFoCarryDoubles * 8 + N * 28 * T * 8 + N * (L + 1) * T * 4 * 8;
-    const size_t slots = 2 + (d.interlayer ? L : 0);
-    const size_t per_row = L * 4 + L * 2 * NM * 8 + L * T * slots * 4 * 8;
+    const size_t sub_bytes = (x && x->substrate_diffuse_modes) ? row.sub_modes * sizeof(double) : 0;
+    const size_t fixed = (row.gl_mu + carry_doubles + row.out + row.layer_backscatter) * sizeof(double) + sub_bytes;
+    const size_t per_row = row.nstream * sizeof(int32_t) + (row.streams + row.integ) * sizeof(double);
     if ((int64_t)(fixed + per_row) > budget) {
         ctx->err = "the workspace budget of the iterative second-order solver is smaller than the buffers of the batch itself plus one pair (" +
                    std::to_string(fixed + per_row) + " bytes)";
@@ -114,13 +111,13 @@ int32_t smrt_second_order_upload_pairs(smrt_dort_ctx* ctx, const smrt_batch* b, 
     smrt_host::gauss_legendre_positive((int)NM, gl.data(), nullptr);
     if (solver_host::upload(ctx, st->gl, gl.data(), NM * sizeof(double), d.gl_mu)) return -1;
     if (sub_bytes && solver_host::upload(ctx, st->submodes, x->substrate_diffuse_modes, sub_bytes, d.sub_modes)) return -1;
-    HIPCHK(st->carry.reserve(N * L * T * kFoCarryDoubles * sizeof(double)));
-    HIPCHK(st->out.reserve(N * 28 * T * sizeof(double)));
-    HIPCHK(st->lb.reserve(N * (L + 1) * T * 4 * sizeof(double)));
-    const size_t R = (size_t)st->chunk_rows;
-    HIPCHK(st->nstream.reserve(R * L * sizeof(int32_t)));
-    HIPCHK(st->streams.reserve(R * L * 2 * NM * sizeof(double)));
-    HIPCHK(st->integ.reserve(R * L * T * slots * 4 * sizeof(double)));
+    const solver_describe::So2Extents n = solver_describe::extents(d, (size_t)st->chunk_rows);
+    HIPCHK(st->carry.reserve(carry_doubles * sizeof(double)));
+    HIPCHK(st->out.reserve(n.out * sizeof(double)));
+    HIPCHK(st->lb.reserve(n.layer_backscatter * sizeof(double)));
+    HIPCHK(st->nstream.reserve(n.nstream * sizeof(int32_t)));
+    HIPCHK(st->streams.reserve(n.streams * sizeof(double)));
+    HIPCHK(st->integ.reserve(n.integ * sizeof(double)));
     if (solver_host::uploads_done(ctx)) return -1;
     fo->carry = (double*)st->carry.p;
     d.fo = *fo;
@@ -185,10 +182,10 @@ int32_t smrt_second_order_download(smrt_dort_ctx* ctx, double* out, int32_t* sta
     if (!st || !st->uploaded) { ctx->err = "no second-order batch uploaded"; return -1; }
     HIPCHK(hipSetDevice(ctx->device));
     const So2Batch& d = st->dev;
-    const size_t N = (size_t)d.fo.n_pairs, L = d.fo.Lmax, T = d.fo.n_theta;
-    if (out) HIPCHK(hipMemcpyAsync(out, d.out, N * 28 * T * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    const solver_describe::So2Extents n = solver_describe::extents(d, (size_t)st->chunk_rows);
+    if (out) HIPCHK(hipMemcpyAsync(out, d.out, n.out * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
     if (backscatter_layer)
-        HIPCHK(hipMemcpyAsync(backscatter_layer, d.layer_backscatter, N * (L + 1) * T * 4 * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+        HIPCHK(hipMemcpyAsync(backscatter_layer, d.layer_backscatter, n.layer_backscatter * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
     return smrt_first_order_download(ctx, nullptr, status, layer_out, nullptr, diag);   // synchronises the stream
 }
 

@@ -96,6 +96,14 @@ int upload(smrt_dort_ctx* ctx, DevBuf& buf, const void* src, size_t bytes, T*& f
     return 0;
 }
 
+// room for `count` elements of a work or output buffer, and the device pointer that writes them
+template <class T>
+int reserve(smrt_dort_ctx* ctx, DevBuf& buf, size_t count, T*& field) {
+    HIPCHK(buf.reserve(count * sizeof(T)));
+    field = (T*)buf.p;
+    return 0;
+}
+
 // the pair list of an *_upload_pairs call (smrt_host::refuse_pairs: null means all pairs, *n_pairs is set)
 inline int check_pairs(smrt_dort_ctx* ctx, const int64_t* pairs, int64_t* n_pairs, int64_t all) {
     const char* why = smrt_host::refuse_pairs(pairs, n_pairs, all);

@@ -10,7 +10,7 @@
 #include <string>
 #include <vector>
 
-#include "successive_order_kernel.hpp"
+#include "solver_describe.hpp"
 #include "solver_host.hpp"
 #include "solver_refusals.hpp"
 
@@ -70,35 +70,27 @@ int32_t smrt_successive_order_upload_pairs(smrt_dort_ctx* ctx, const smrt_batch*
     SuccessiveOrderState* st = ctx->successive_order;
     st->uploaded = st->launched = false;
     st->budget = workspace_budget_bytes > 0 ? workspace_budget_bytes : kSoDefaultBudget;
-    const size_t S = b->n_snowpacks, L = b->n_layers_max, F = b->n_frequencies, T = b->n_theta, N = (size_t)n_pairs;
-    const size_t SL = S * L * sizeof(double), FS = F * S, NM = b->n_max_stream, NO = n_iteration_max;
+    SoBatch d = solver_describe::successive_order(b, n_iteration_max, relative_tolerance, n_pairs);
+    const solver_describe::SoExtents n = solver_describe::extents(d);
     // everything but the chunk buffer, counted before anything is reserved: the budget is checked first
-    const size_t Dh = 2 * NM;
-    const size_t out_bytes[] = {(size_t)SO_ROWS * L * N * 8, N * L * 4, N * L * 4, N * L * SO_VECS * Dh * 8, N * L * 8, N * 8,
-                                N * (NO + 1) * 2 * T * 8, N * 4, N * L * 5 * 8, N * (1 + NM) * 8, N * NO * 8, N * 4};
-    size_t fixed = S * 4 + 5 * SL + (b->liquid_water ? SL : 0) + (b->layer_kind ? S * L * 4 : 0) + F * 8 + T * 8 + NM * 8 +
-                   (b->substrate_kind != SMRT_SUBSTRATE_NONE ? 2 * smrt_host::substrate_array_doubles(b) * 8 + S * 8 : 0) + (pairs ? N * 8 : 0);
+    const size_t out_bytes[] = {n.stage * 8, n.nsub * 4, n.nstream * 4, n.vec * 8, n.srcterm * 8, n.ws_off * 8,
+                                n.out * 8, n.status * 4, n.layer_out * 8, n.streams * 8, n.maxrad * 8, n.orders * 4};
+    size_t fixed = solver_describe::input_bytes(b, solver_describe::inputs(d, pairs != nullptr)) + (n.theta + n.gl_mu + n.sub_T) * 8;
     for (size_t v : out_bytes) fixed += v;
     if ((int64_t)fixed >= st->budget) {
         ctx->err = "the workspace budget of the successive_order solver is smaller than the buffers of the batch itself (" +
                    std::to_string(fixed) + " bytes)";
         return -1;
     }
-    SoBatch d{};
-    d.S = (int)S; d.Lmax = (int)L; d.F = (int)F; d.n_theta = (int)T;
-    d.emmodel = b->emmodel; d.micro = b->microstructure; d.sub_kind = b->substrate_kind; d.nmax = (int)NM;
-    d.n_iter = n_iteration_max; d.rj = b->rayleigh_jeans ? 1 : 0; d.nsamp = azimuth_samples(b->m_max);
-    d.rtol = relative_tolerance;
-    d.n_pairs = n_pairs;
     using solver_host::upload;
     if (solver_host::upload_batch(ctx, st, b, pairs, d)) return -1;
-    if (upload(ctx, st->theta, b->theta, T * sizeof(double), d.theta)) return -1;
-    std::vector<double> subT(S, 0.0);   // (zeros where the caller gives no substrate temperature)
-    for (size_t s = 0; s < S && b->substrate_temperature; ++s) subT[s] = b->substrate_temperature[s];
-    if (b->substrate_kind != SMRT_SUBSTRATE_NONE && upload(ctx, st->subT, subT.data(), S * sizeof(double), d.sub_T)) return -1;
-    std::vector<double> gl(NM);
-    smrt_host::gauss_legendre_positive((int)NM, gl.data(), nullptr);
-    if (upload(ctx, st->gl, gl.data(), NM * sizeof(double), d.gl_mu)) return -1;
+    if (upload(ctx, st->theta, b->theta, n.theta * sizeof(double), d.theta)) return -1;
+    std::vector<double> subT(d.S, 0.0);   // (zeros where the caller gives no substrate temperature)
+    for (size_t s = 0; s < subT.size() && b->substrate_temperature; ++s) subT[s] = b->substrate_temperature[s];
+    if (n.sub_T && upload(ctx, st->subT, subT.data(), n.sub_T * sizeof(double), d.sub_T)) return -1;
+    std::vector<double> gl(n.gl_mu);
+    smrt_host::gauss_legendre_positive(d.nmax, gl.data(), nullptr);
+    if (upload(ctx, st->gl, gl.data(), n.gl_mu * sizeof(double), d.gl_mu)) return -1;
     DevBuf* outs[] = {&st->stage, &st->nsub, &st->nstream, &st->vec, &st->srcterm, &st->wsoff, &st->out, &st->status, &st->layer,
                       &st->streams, &st->maxrad, &st->orders};
     for (size_t k = 0; k < sizeof(outs) / sizeof(outs[0]); ++k) HIPCHK(outs[k]->reserve(out_bytes[k]));
@@ -133,8 +125,9 @@ int32_t smrt_successive_order_launch(smrt_dort_ctx* ctx) {
     HIPCHK(hipMemcpyAsync(st->nsub_host.data(), d.nsub, (size_t)(N * L) * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
     HIPCHK(hipStreamSynchronize(ctx->stream));
     // the chunk plan: consecutive rows whose Wt matrices and workspaces fit what the budget leaves
+    const solver_describe::SoExtents n = solver_describe::extents(d);
     const long long Dp = so_dp(d.nmax), Dh = 2 * d.nmax;
-    const long long wt_pair = L * Dp * Dp;                       // doubles
+    const long long wt_pair = (long long)n.wt_pair;              // doubles
     const long long avail = (st->budget - (int64_t)st->fixed_bytes) / 8;   // doubles
     std::vector<long long> ws_off((size_t)N, 0), begin, count, ws_total;
     long long cur_ws = 0, cur_n = 0, cur_begin = 0, largest = 0;
@@ -160,7 +153,7 @@ int32_t smrt_successive_order_launch(smrt_dort_ctx* ctx) {
     if (largest > 0) HIPCHK(st->chunk.reserve((size_t)largest * 8));
     HIPCHK(hipMemcpyAsync(st->wsoff.p, ws_off.data(), (size_t)N * sizeof(long long), hipMemcpyHostToDevice, ctx->stream));
     HIPCHK(hipStreamSynchronize(ctx->stream));   // (ws_off is a local vector)
-    const size_t lds = (size_t)so_lds_doubles(d.nmax, d.n_theta) * sizeof(double);
+    const size_t lds = n.lds_sweep;
     for (size_t c = 0; c < begin.size(); ++c) {
         d.chunk_begin = begin[c]; d.chunk_count = count[c];
         d.wt = (double*)st->chunk.p;
@@ -206,16 +199,17 @@ int32_t smrt_successive_order_download(smrt_dort_ctx* ctx, double* out, int32_t*
     if (!st || !st->launched) { ctx->err = "no successive-order launch to download"; return -1; }
     HIPCHK(hipSetDevice(ctx->device));
     const SoBatch& d = st->dev;
-    const size_t N = (size_t)d.n_pairs, L = d.Lmax, row = (size_t)(d.n_iter + 1) * 2 * d.n_theta, NO = d.n_iter, NS = 1 + d.nmax;
-    if (out) HIPCHK(hipMemcpyAsync(out, d.out, N * row * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-    if (status) HIPCHK(hipMemcpyAsync(status, d.status, N * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
-    if (layer_out) HIPCHK(hipMemcpyAsync(layer_out, d.layer_out, N * L * 5 * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-    if (streams) HIPCHK(hipMemcpyAsync(streams, d.streams, N * NS * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-    if (max_radiance) HIPCHK(hipMemcpyAsync(max_radiance, d.maxrad, N * NO * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-    if (orders) HIPCHK(hipMemcpyAsync(orders, d.orders, N * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
+    const solver_describe::SoExtents n = solver_describe::extents(d);
+    if (out) HIPCHK(hipMemcpyAsync(out, d.out, n.out * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    if (status) HIPCHK(hipMemcpyAsync(status, d.status, n.status * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
+    if (layer_out) HIPCHK(hipMemcpyAsync(layer_out, d.layer_out, n.layer_out * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    if (streams) HIPCHK(hipMemcpyAsync(streams, d.streams, n.streams * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    if (max_radiance) HIPCHK(hipMemcpyAsync(max_radiance, d.maxrad, n.maxrad * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    if (orders) HIPCHK(hipMemcpyAsync(orders, d.orders, n.orders * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
     HIPCHK(hipStreamSynchronize(ctx->stream));
-    if (sublayers) std::memcpy(sublayers, st->nsub_host.data(), N * L * sizeof(int32_t));
+    if (sublayers) std::memcpy(sublayers, st->nsub_host.data(), n.nsub * sizeof(int32_t));
     for (long long i : st->deep) {   // the rows no kernel touched
+        const size_t N = (size_t)d.n_pairs, row = n.out / N, NO = n.maxrad / N, NS = n.streams / N;   // per pair
         if (out) for (size_t k = 0; k < row; ++k) out[(size_t)i * row + k] = NAN;
         if (status) status[i] = ST_DEPTH;
         if (streams) for (size_t k = 0; k < NS; ++k) streams[(size_t)i * NS + k] = 0.0;

@@ -11,7 +11,7 @@
 #include <string>
 #include <vector>
 
-#include "successive_order_active_kernel.hpp"
+#include "solver_describe.hpp"
 #include "solver_host.hpp"
 #include "solver_refusals.hpp"
 
@@ -81,35 +81,26 @@ int32_t smrt_so_active_upload_pairs(smrt_dort_ctx* ctx, const smrt_batch* b, int
     SuccessiveOrderActiveState* st = ctx->successive_order_active;
     st->uploaded = st->launched = false;
     st->budget = workspace_budget_bytes > 0 ? workspace_budget_bytes : kSoaDefaultBudget;
-    const size_t S = b->n_snowpacks, L = b->n_layers_max, F = b->n_frequencies, T = n_theta_inc, N = (size_t)n_pairs;
-    const size_t SL = S * L * sizeof(double), FS = F * S, NM = b->n_max_stream, NO = n_iteration_max, NP = m_max + 2;
-    const size_t Dh = 3 * NM, CM = soa_max_columns(incident_npol, n_theta_inc, (int)NM);
+    SoaBatch a = solver_describe::successive_order_active(b, n_iteration_max, relative_tolerance, n_theta_inc, incident_npol, m_max, n_pairs);
+    SoBatch& d = a.so;
+    const solver_describe::SoaExtents n = solver_describe::extents(a);
     // everything but the chunk buffer, counted before anything is reserved: the budget is checked first
-    const size_t out_bytes[] = {(size_t)SO_ROWS * L * N * 8, N * L * 4, N * L * 4, N * L * SOA_VECS * Dh * 8, N * 2 * Dh * 8, N * 8,
-                                N * 9 * T * (NO + 1) * 8, N * 4, N * L * 5 * 8, N * (1 + NM) * 8, N * NP * NO * 8, N * NP * 4,
-                                N * NP * NO * 3 * CM * 8, N * (1 + NM) * 4};
-    size_t fixed = S * 4 + 5 * SL + (b->liquid_water ? SL : 0) + (b->layer_kind ? S * L * 4 : 0) + F * 8 + T * 8 + NM * 8 +
-                   (b->substrate_kind != SMRT_SUBSTRATE_NONE ? 2 * FS * 8 : 0) + (pairs ? N * 8 : 0);
+    const size_t out_bytes[] = {n.stage * 8, n.nsub * 4, n.nstream * 4, n.vec * 8, n.air * 8, n.ws_off * 8,
+                                n.out * 8, n.status * 4, n.layer_out * 8, n.streams * 8, n.maxrad * 8, n.orders * 4,
+                                n.back * 8, n.inc * 4};
+    size_t fixed = solver_describe::input_bytes(b, solver_describe::inputs(d, pairs != nullptr)) + (n.theta + n.gl_mu) * 8;
     for (size_t v : out_bytes) fixed += v;
     if ((int64_t)fixed >= st->budget) {
         ctx->err = "the workspace budget of the successive_order_backscatter solver is smaller than the buffers of the batch itself (" +
                    std::to_string(fixed) + " bytes)";
         return -1;
     }
-    SoaBatch a{};
-    SoBatch& d = a.so;
-    d.S = (int)S; d.Lmax = (int)L; d.F = (int)F; d.n_theta = (int)T;
-    d.emmodel = b->emmodel; d.micro = b->microstructure; d.sub_kind = b->substrate_kind; d.nmax = (int)NM;
-    d.n_iter = n_iteration_max; d.rj = 0; d.nsamp = azimuth_samples(m_max);
-    d.rtol = relative_tolerance;
-    d.n_pairs = n_pairs;
-    a.npi = incident_npol; a.m_max = m_max; a.Cmax = (int)CM; a.phi = b->phi;
     using solver_host::upload;
     if (solver_host::upload_batch(ctx, st, b, pairs, d)) return -1;
-    if (upload(ctx, st->theta, theta_inc, T * sizeof(double), d.theta)) return -1;
-    std::vector<double> gl(NM);
-    smrt_host::gauss_legendre_positive((int)NM, gl.data(), nullptr);
-    if (upload(ctx, st->gl, gl.data(), NM * sizeof(double), d.gl_mu)) return -1;
+    if (upload(ctx, st->theta, theta_inc, n.theta * sizeof(double), d.theta)) return -1;
+    std::vector<double> gl(n.gl_mu);
+    smrt_host::gauss_legendre_positive(d.nmax, gl.data(), nullptr);
+    if (upload(ctx, st->gl, gl.data(), n.gl_mu * sizeof(double), d.gl_mu)) return -1;
     DevBuf* outs[] = {&st->stage, &st->nsub, &st->nstream, &st->vec, &st->air, &st->wsoff, &st->out, &st->status, &st->layer,
                       &st->streams, &st->maxrad, &st->orders, &st->back, &st->inc};
     for (size_t k = 0; k < sizeof(outs) / sizeof(outs[0]); ++k) HIPCHK(outs[k]->reserve(out_bytes[k]));
@@ -146,8 +137,8 @@ int32_t smrt_so_active_launch(smrt_dort_ctx* ctx) {
     HIPCHK(hipStreamSynchronize(ctx->stream));
     // the chunk plan: consecutive rows whose Wt matrices ((m_max + 1) x Lmax x Dp^2 per pair) and workspaces ((m_max + 2) passes
     // per pair, sized for the largest column count) fit what the budget leaves
-    const long long Dp = soa_dp(d.nmax);
-    const long long wt_pair = M * L * Dp * Dp;                   // doubles
+    const solver_describe::SoaExtents n = solver_describe::extents(a);
+    const long long wt_pair = (long long)n.wt_pair;              // doubles
     const long long avail = (st->budget - (int64_t)st->fixed_bytes) / 8;   // doubles
     std::vector<long long> ws_off((size_t)N, 0), begin, count;
     long long cur_ws = 0, cur_n = 0, cur_begin = 0, largest = 0;
@@ -173,7 +164,7 @@ int32_t smrt_so_active_launch(smrt_dort_ctx* ctx) {
     if (largest > 0) HIPCHK(st->chunk.reserve((size_t)largest * 8));
     HIPCHK(hipMemcpyAsync(st->wsoff.p, ws_off.data(), (size_t)N * sizeof(long long), hipMemcpyHostToDevice, ctx->stream));
     HIPCHK(hipStreamSynchronize(ctx->stream));   // (ws_off is a local vector)
-    const size_t lds = (size_t)soa_lds_doubles(d.nmax) * sizeof(double);
+    const size_t lds = n.lds_sweep;
     const long long row = 9LL * d.n_theta * (d.n_iter + 1);
     for (size_t c = 0; c < begin.size(); ++c) {
         d.chunk_begin = begin[c]; d.chunk_count = count[c];
@@ -226,17 +217,17 @@ int32_t smrt_so_active_download(smrt_dort_ctx* ctx, double* out, int32_t* status
     if (!st || !st->launched) { ctx->err = "no successive-order backscatter launch to download"; return -1; }
     HIPCHK(hipSetDevice(ctx->device));
     const SoBatch& d = st->dev.so;
-    const size_t N = (size_t)d.n_pairs, L = d.Lmax, row = (size_t)9 * d.n_theta * (d.n_iter + 1), NS = 1 + d.nmax;
-    const size_t NP = st->dev.m_max + 2, NO = NP * d.n_iter;
-    if (out) HIPCHK(hipMemcpyAsync(out, d.out, N * row * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-    if (status) HIPCHK(hipMemcpyAsync(status, d.status, N * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
-    if (layer_out) HIPCHK(hipMemcpyAsync(layer_out, d.layer_out, N * L * 5 * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-    if (streams) HIPCHK(hipMemcpyAsync(streams, d.streams, N * NS * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-    if (max_radiance) HIPCHK(hipMemcpyAsync(max_radiance, d.maxrad, N * NO * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-    if (orders) HIPCHK(hipMemcpyAsync(orders, d.orders, N * NP * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
+    const solver_describe::SoaExtents n = solver_describe::extents(st->dev);
+    if (out) HIPCHK(hipMemcpyAsync(out, d.out, n.out * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    if (status) HIPCHK(hipMemcpyAsync(status, d.status, n.status * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
+    if (layer_out) HIPCHK(hipMemcpyAsync(layer_out, d.layer_out, n.layer_out * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    if (streams) HIPCHK(hipMemcpyAsync(streams, d.streams, n.streams * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    if (max_radiance) HIPCHK(hipMemcpyAsync(max_radiance, d.maxrad, n.maxrad * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    if (orders) HIPCHK(hipMemcpyAsync(orders, d.orders, n.orders * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
     HIPCHK(hipStreamSynchronize(ctx->stream));
-    if (sublayers) std::memcpy(sublayers, st->nsub_host.data(), N * L * sizeof(int32_t));
+    if (sublayers) std::memcpy(sublayers, st->nsub_host.data(), n.nsub * sizeof(int32_t));
     for (long long i : st->deep) {   // the rows no kernel touched
+        const size_t N = (size_t)d.n_pairs, row = n.out / N, NS = n.streams / N, NO = n.maxrad / N, NP = n.orders / N;   // per pair
         if (out) for (size_t k = 0; k < row; ++k) out[(size_t)i * row + k] = NAN;
         if (status) status[i] = ST_DEPTH;
         if (streams) for (size_t k = 0; k < NS; ++k) streams[(size_t)i * NS + k] = 0.0;

@@ -1,12 +1,11 @@
 // The device arithmetic of the nadir SAR altimetry solver (smrt_amd/csrc/nadir_sar_altimetry_kernel.hpp) compiled for the CPU:
-// a "workgroup" of one thread, scans as running sums.  Built by tests/test_nadir_sar_altimetry_cpu.py:
+// a "workgroup" of one thread, scans as running sums.  Built by tests/host_build.py:
 //   g++ -O2 -std=c++17 -shared -fPIC -DSMRT_HOST_EMU -I tests/hostemu -o libsmrt_sar_host.so nadir_sar_altimetry_host.cpp
-#include <cmath>
 #include <cstdint>
 #include <vector>
 
 #include "../../smrt_amd/csrc/solver_refusals.hpp"
-#include "../../include/smrt_dort.h"
+#include "host_batch.hpp"
 
 using namespace smrt;
 
@@ -17,43 +16,24 @@ int32_t smrt_sar_host_run(const smrt_batch* b, const smrt_sar_params* p, double*
     if (!out || !status || !z_gate || !layer_out || !vertical || !echo) return -1;
     if (solver_refusals::nadir_sar_altimetry(b, p)) return -1;
     const long long NP = b->n_snowpacks;
-    const int L = b->n_layers_max;
-    std::vector<int> nl(b->n_layers, b->n_layers + b->n_snowpacks), kinds;
-    if (b->layer_kind) kinds.assign(b->layer_kind, b->layer_kind + (size_t)b->n_snowpacks * L);
-    SarBatch d{};
+    host_batch::Inputs in;
+    smrt_sar_params dinardo = *p;   // (this library runs the route of Dinardo18 whatever the parameters name)
+    dinardo.delay_doppler_model = SMRT_SAR_DINARDO18;
+    SarBatch d = solver_describe::nadir_sar_altimetry(b, &dinardo, NP);
     LrmBatch& lb = d.lrm;
     FoBatch& fo = lb.fo;
-    fo.S = b->n_snowpacks; fo.Lmax = L; fo.F = 1; fo.n_theta = 1;
-    fo.emmodel = b->emmodel; fo.micro = b->microstructure; fo.n_pairs = NP;
-    fo.n_layers = nl.data();
-    fo.thickness = b->thickness; fo.frac_volume = b->frac_volume; fo.temperature = b->temperature;
-    fo.p1 = b->micro_p1; fo.p2 = b->micro_p2; fo.frequency = b->frequency; fo.liquid_water = b->liquid_water;
-    fo.layer_kind = b->layer_kind ? kinds.data() : nullptr;
-    fo.host_layer = b->host_layer; fo.host_coeff = b->host_iba_coeff;
-    lb.ngate = p->ngate; lb.os = p->oversampling_time; lb.n_mu = 1;
-    lb.oversampled = p->return_oversampled ? 1 : 0;
-    lb.N = p->ngate * p->oversampling_time;
-    lb.rows = 1; lb.out_rows = 1; lb.n_out = lb.oversampled ? lb.N : lb.ngate; lb.sar = 1;
-    lb.altitude = p->altitude; lb.bandwidth = p->pulse_bandwidth; lb.nominal_gate = p->nominal_gate;
+    in.bind(b, nullptr, fo);
+    const solver_describe::SarExtents n = solver_describe::extents(d);
     lb.itf = p->boundary_values;
-    d.ndoppler = p->ndoppler; d.osd = p->oversampling_doppler; d.ND = p->ndoppler * p->oversampling_doppler;
-    d.out_rows = p->n_rows; d.n_tab = p->n_tables; d.n_t = lb.n_out; d.n_d = lb.oversampled ? d.ND : d.ndoppler;
-    d.prf = p->pulse_repetition_frequency; d.wavelength = p->wavelength; d.velocity = p->velocity; d.alpha = p->alpha;
-    d.pitch = p->pitch_angle; d.roll = p->roll_angle; d.sigma_p = p->sigma_p; d.theta_lim = p->theta_lim;
-    d.gamma_x = p->gamma_x; d.gamma_y = p->gamma_y; d.l_gamma = p->l_gamma; d.lz = p->lz; d.pu = p->pu; d.nu_coherent = p->nu_coherent;
-    std::vector<int> tab_index(p->table_index, p->table_index + b->n_snowpacks);
-    std::vector<int> row_map(p->row_map, p->row_map + (size_t)b->n_snowpacks * (2 * (L + 1) + 2));
-    d.tab_sigma = p->table_sigma; d.tab_index = tab_index.data(); d.row_map = row_map.data();
-    std::vector<double> stage((size_t)FO_ROWS * L * NP, 0.0), bs((size_t)L * NP, 0.0), prefix((size_t)NP * LRM_PREFIX_ROWS * (L + 1), 0.0);
-    std::vector<double> tables((size_t)d.n_tab * 2 * lb.N * d.ND);
-    std::vector<unsigned char> lds(lrm_vertical_lds_bytes(lb.N, L) + sar_combine_lds_bytes(lb.N, d.osd));
+    d.tab_sigma = p->table_sigma; d.tab_index = p->table_index; d.row_map = p->row_map;
+    std::vector<double> stage(n.lrm.stage, 0.0), bs(n.lrm.bs, 0.0), prefix(n.lrm.prefix, 0.0), tables(n.tables);
+    std::vector<unsigned char> lds(n.lrm.lds_vertical + n.lds_combine);
     fo.stage = stage.data(); fo.layer_out = layer_out;
     lb.bs = bs.data(); lb.prefix = prefix.data(); lb.vsd = vertical; lb.z_gate = z_gate; lb.status = status;
     d.tables = tables.data(); d.echo = echo; d.out = out;
-    LrmLane ln;
-    ln.tid = 0; ln.nt = 1; ln.wsum = nullptr;
+    LrmLane ln{0, 1, nullptr};
     for (long long i = 0; i < NP; ++i)
-        for (int l = 0; l < L; ++l) lrm_layer_item(lb, i, l);
+        for (int l = 0; l < fo.Lmax; ++l) lrm_layer_item(lb, i, l);
     for (long long i = 0; i < NP; ++i) { lrm_vertical_pair(lb, i, ln, lds.data()); sar_boundary_pair(d, i, 0, 1); }
     for (long long k = 0; k < (long long)d.n_tab * lb.N * d.ND; ++k) sar_table_item(d, k);
     for (long long i = 0; i < NP; ++i)

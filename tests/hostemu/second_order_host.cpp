@@ -1,13 +1,11 @@
 // The device arithmetic of the iterative second-order solver (smrt_amd/csrc/second_order_kernel.hpp, on top of
 // first_order_kernel.hpp) compiled for the CPU: the per-item functions in plain loops, the wavefront function of the
-// integrals under the fiber emulator (64 fibers).  Built by tests/test_second_order_cpu.py:
+// integrals under the fiber emulator (64 fibers).  Built by tests/host_build.py:
 //   g++ -O2 -std=c++17 -shared -fPIC -DSMRT_HOST_EMU -I tests/hostemu -o libsmrt_second_order_host.so second_order_host.cpp
 #include <cstdint>
 #include <vector>
 
-#include "../../smrt_amd/csrc/second_order_kernel.hpp"
-#include "../../smrt_amd/csrc/dort_host_common.hpp"
-#include "../../include/smrt_dort.h"
+#include "host_batch.hpp"
 
 using namespace smrt;
 
@@ -31,41 +29,28 @@ int32_t smrt_second_order_host_run(const smrt_batch* b, const smrt_second_order_
     if (!b || !out || !status || !backscatter_layer) return -1;
     if (b->n_max_stream < 2 || b->m_max < 1 || b->m_max > kSo2MaxModes) return -1;
     const long long N = (long long)b->n_snowpacks * b->n_frequencies;
-    const int L = b->n_layers_max, T = b->n_theta, NM = b->n_max_stream;
     const smrt_first_order_extras* x1 = x ? x->first_order : nullptr;
-    std::vector<double> stage((size_t)FO_ROWS * L * N, 0.0), fo_out((size_t)N * 16 * T), fo_lb((size_t)N * (L + 1) * T * 4);
-    std::vector<double> carry((size_t)N * L * T * kFoCarryDoubles, 0.0), gl(NM);
-    std::vector<int> nl(b->n_layers, b->n_layers + b->n_snowpacks), kinds, slots;
-    if (b->layer_kind) kinds.assign(b->layer_kind, b->layer_kind + (size_t)b->n_snowpacks * L);
-    So2Batch d{};
+    host_batch::Inputs in;
+    So2Batch d = solver_describe::second_order(b, x, N);
     FoBatch& f = d.fo;
-    f.S = b->n_snowpacks; f.Lmax = L; f.F = b->n_frequencies; f.n_theta = T;
-    f.emmodel = b->emmodel; f.micro = b->microstructure; f.sub_kind = b->substrate_kind;
-    f.n_pairs = N;
-    f.n_layers = nl.data();
-    f.thickness = b->thickness; f.frac_volume = b->frac_volume; f.temperature = b->temperature;
-    f.p1 = b->micro_p1; f.p2 = b->micro_p2; f.frequency = b->frequency; f.theta = b->theta; f.liquid_water = b->liquid_water;
-    f.layer_kind = b->layer_kind ? kinds.data() : nullptr;
-    f.host_layer = b->host_layer; f.host_coeff = b->host_iba_coeff;
-    f.sub_p1 = b->substrate_p1; f.sub_p2 = b->substrate_p2;
-    if (x1 && x1->host_interface_slot) {
-        slots.assign(x1->host_interface_slot, x1->host_interface_slot + (size_t)N * (L + 1));
-        f.itf_slot = slots.data(); f.itf_values = x1->host_interface_values; f.n_slots = x1->n_interface_slots;
-    }
+    in.bind(b, nullptr, f);
+    const int L = f.Lmax, T = f.n_theta;
+    const solver_describe::FoExtents nf = solver_describe::extents(f);
+    const solver_describe::So2Extents n = solver_describe::extents(d, (size_t)N);   // one chunk
+    std::vector<double> stage(nf.stage, 0.0), fo_out(nf.out), fo_lb(nf.layer_backscatter), carry(nf.carry, 0.0), gl(n.gl_mu);
+    f.theta = b->theta;
+    if (x1 && x1->host_interface_slot) { f.itf_slot = x1->host_interface_slot; f.itf_values = x1->host_interface_values; }
     f.stage = stage.data(); f.out = fo_out.data(); f.status = status;
     f.layer_out = layer_out; f.layer_backscatter = fo_lb.data(); f.diag = diag; f.carry = carry.data();
     for (long long i = 0; i < N; ++i)
         for (int l = 0; l < L; ++l) first_order_layer_item(f, i, l);
     for (long long i = 0; i < N; ++i)
         for (int t = 0; t < T; ++t) first_order_angle_item(f, i, t);
-    smrt_host::gauss_legendre_positive(NM, gl.data(), nullptr);
-    d.nmax = NM; d.m_max = b->m_max; d.nsamp = azimuth_samples(b->m_max);
-    d.interlayer = (x && x->compute_scattering_interlayer) ? 1 : 0;
+    smrt_host::gauss_legendre_positive(d.nmax, gl.data(), nullptr);
     d.chunk_begin = 0; d.chunk_count = N;
     d.gl_mu = gl.data(); d.sub_modes = x ? x->substrate_diffuse_modes : nullptr;
-    const int nslots = 2 + (d.interlayer ? L : 0);
-    std::vector<int> nstream((size_t)N * L, 0);
-    std::vector<double> streams((size_t)N * L * 2 * NM, 0.0), integ((size_t)N * L * T * nslots * 4, 0.0);
+    std::vector<int> nstream(n.nstream, 0);
+    std::vector<double> streams(n.streams, 0.0), integ(n.integ, 0.0);
     d.nstream = nstream.data(); d.streams = streams.data(); d.integ = integ.data();
     d.out = out; d.layer_backscatter = backscatter_layer;
     for (long long i = 0; i < N; ++i)

@@ -1,13 +1,11 @@
 // The device arithmetic of the successive-order backscatter solver (smrt_amd/csrc/successive_order_active_kernel.hpp) compiled
 // for the CPU: the per-(pair, layer) and per-output-element functions in plain loops, the two workgroup functions under the
-// fiber emulator (256 fibers, the MFMA in its gfx950 lane layout).  Built by tests/test_successive_order_active_cpu.py:
+// fiber emulator (256 fibers, the MFMA in its gfx950 lane layout).  Built by tests/host_build.py:
 //   g++ -O2 -std=c++17 -shared -fPIC -DSMRT_HOST_EMU -I tests/hostemu -o libsmrt_so_active_host.so successive_order_active_host.cpp
 #include <cstdint>
 #include <vector>
 
-#include "../../smrt_amd/csrc/successive_order_active_kernel.hpp"
-#include "../../smrt_amd/csrc/dort_host_common.hpp"
-#include "../../include/smrt_dort.h"
+#include "host_batch.hpp"
 
 using namespace smrt;
 
@@ -21,39 +19,31 @@ int32_t smrt_so_active_host_run(const smrt_batch* b, int32_t n_iter, double rtol
     if (!b || !out || !status || !layer_out || !streams || !sublayers || !max_radiance || !orders || n_iter < 1) return -1;
     if (b->n_max_stream < 2 || b->n_max_stream > kSoMaxStream || n_theta_inc < 1 || npi < 1 || npi > 3 || m_max < 0) return -1;
     const long long N = (long long)b->n_snowpacks * b->n_frequencies;
-    const int L = b->n_layers_max, NM = b->n_max_stream, Dh = 3 * NM, Dp = soa_dp(NM), M = m_max + 1, NP = m_max + 2;
-    const int CM = soa_max_columns(npi, n_theta_inc, NM);
-    std::vector<int> nl(b->n_layers, b->n_layers + b->n_snowpacks), kinds, nsub((size_t)N * L), nstream((size_t)N * L, 0);
-    if (b->layer_kind) kinds.assign(b->layer_kind, b->layer_kind + (size_t)b->n_snowpacks * L);
-    std::vector<double> stage((size_t)SO_ROWS * L * N, 0.0), vec((size_t)N * L * SOA_VECS * Dh, 0.0), air((size_t)N * 2 * Dh, 0.0), gl(NM);
-    std::vector<double> back((size_t)N * NP * n_iter * 3 * CM, 0.0);
-    std::vector<int> inc((size_t)N * (1 + NM), 0);
-    smrt_host::gauss_legendre_positive(NM, gl.data(), nullptr);
-    SoaBatch a{};
+    host_batch::Inputs in;
+    SoaBatch a = solver_describe::successive_order_active(b, n_iter, rtol, n_theta_inc, npi, m_max, N);
     SoBatch& d = a.so;
-    d.S = b->n_snowpacks; d.Lmax = L; d.F = b->n_frequencies; d.n_theta = n_theta_inc;
-    d.emmodel = b->emmodel; d.micro = b->microstructure; d.sub_kind = b->substrate_kind; d.nmax = NM;
-    d.n_iter = n_iter; d.rj = 0; d.nsamp = azimuth_samples(m_max); d.rtol = rtol;
-    d.n_pairs = N; d.chunk_begin = 0; d.chunk_count = N;
-    d.n_layers = nl.data();
-    d.thickness = b->thickness; d.frac_volume = b->frac_volume; d.temperature = b->temperature;
-    d.p1 = b->micro_p1; d.p2 = b->micro_p2; d.frequency = b->frequency; d.theta = theta_inc; d.liquid_water = b->liquid_water;
-    d.layer_kind = b->layer_kind ? kinds.data() : nullptr;
-    d.sub_p1 = b->substrate_p1; d.sub_p2 = b->substrate_p2; d.gl_mu = gl.data();
+    in.bind(b, nullptr, d);
+    const solver_describe::SoaExtents n = solver_describe::extents(a);
+    const int L = d.Lmax, M = m_max + 1, NP = m_max + 2;
+    std::vector<int> nsub(n.nsub), nstream(n.nstream, 0), inc(n.inc, 0);
+    std::vector<double> stage(n.stage, 0.0), vec(n.vec, 0.0), air(n.air, 0.0), back(n.back, 0.0), gl(n.gl_mu);
+    smrt_host::gauss_legendre_positive(d.nmax, gl.data(), nullptr);
+    d.chunk_begin = 0; d.chunk_count = N;
+    d.theta = theta_inc; d.gl_mu = gl.data();
     d.stage = stage.data(); d.nsub = nsub.data(); d.nstream = nstream.data(); d.vec = vec.data();
     d.out = out; d.status = status; d.layer_out = layer_out; d.streams = streams; d.maxrad = max_radiance; d.orders = orders;
-    a.npi = npi; a.m_max = m_max; a.Cmax = CM; a.phi = b->phi; a.air = air.data(); a.back = back.data(); a.inc = inc.data();
+    a.air = air.data(); a.back = back.data(); a.inc = inc.data();
     for (long long i = 0; i < N; ++i)
         for (int l = 0; l < L; ++l) so_layer_item(d, i, l);
-    std::vector<long long> ws_off((size_t)N);
+    std::vector<long long> ws_off(n.ws_off);
     long long total = 0;
     for (long long i = 0; i < N; ++i) {
         long long n_sub = 0, n_lay = 0;
         for (int l = 0; l < L; ++l) { n_sub += nsub[(size_t)i * L + l]; n_lay += nsub[(size_t)i * L + l] > 0; sublayers[i * L + l] = nsub[(size_t)i * L + l]; }
         ws_off[(size_t)i] = total;
-        total += NP * soa_pass_doubles(n_sub, n_lay, CM, NM);
+        total += NP * soa_pass_doubles(n_sub, n_lay, a.Cmax, d.nmax);
     }
-    std::vector<double> wt((size_t)N * M * L * Dp * Dp, 0.0), ws((size_t)total, 0.0), lds((size_t)soa_lds_doubles(NM), 0.0);
+    std::vector<double> wt((size_t)N * n.wt_pair, 0.0), ws((size_t)total, 0.0), lds(n.lds_sweep / sizeof(double), 0.0);
     d.wt = wt.data(); d.ws = ws.data(); d.ws_off = ws_off.data();
     for (long long i = 0; i < N; ++i)
         for (int m = 0; m < M; ++m)

@@ -1,13 +1,11 @@
 // The device arithmetic of the successive-order solver (smrt_amd/csrc/successive_order_kernel.hpp) compiled for the CPU:
 // the per-(pair, layer) function in a plain loop, the two workgroup functions under the fiber emulator (256 fibers, the
-// MFMA in its gfx950 lane layout).  Built by tests/test_successive_order_cpu.py:
+// MFMA in its gfx950 lane layout).  Built by tests/host_build.py:
 //   g++ -O2 -std=c++17 -shared -fPIC -DSMRT_HOST_EMU -I tests/hostemu -o libsmrt_successive_order_host.so successive_order_host.cpp
 #include <cstdint>
 #include <vector>
 
-#include "../../smrt_amd/csrc/successive_order_kernel.hpp"
-#include "../../smrt_amd/csrc/dort_host_common.hpp"
-#include "../../include/smrt_dort.h"
+#include "host_batch.hpp"
 
 using namespace smrt;
 
@@ -19,28 +17,23 @@ int32_t smrt_successive_order_host_run(const smrt_batch* b, int32_t n_iter, doub
     if (!b || !out || !status || !layer_out || !streams || !sublayers || !max_radiance || !orders || n_iter < 1) return -1;
     if (b->n_max_stream < 2 || b->n_max_stream > kSoMaxStream) return -1;
     const long long N = (long long)b->n_snowpacks * b->n_frequencies;
-    const int L = b->n_layers_max, NM = b->n_max_stream, Dh = 2 * NM, Dp = so_dp(NM);
-    std::vector<int> nl(b->n_layers, b->n_layers + b->n_snowpacks), kinds, nsub((size_t)N * L), nstream((size_t)N * L, 0);
-    if (b->layer_kind) kinds.assign(b->layer_kind, b->layer_kind + (size_t)b->n_snowpacks * L);
-    std::vector<double> stage((size_t)SO_ROWS * L * N, 0.0), vec((size_t)N * L * SO_VECS * Dh, 0.0), srcterm((size_t)N * L, 0.0), gl(NM);
-    std::vector<double> subT(b->n_snowpacks, 0.0);
+    host_batch::Inputs in;
+    SoBatch d = solver_describe::successive_order(b, n_iter, rtol, N);
+    in.bind(b, nullptr, d);
+    const solver_describe::SoExtents n = solver_describe::extents(d);
+    const int L = d.Lmax, Dh = 2 * d.nmax, Dp = so_dp(d.nmax);
+    std::vector<int> nsub(n.nsub), nstream(n.nstream, 0);
+    std::vector<double> stage(n.stage, 0.0), vec(n.vec, 0.0), srcterm(n.srcterm, 0.0), gl(n.gl_mu);
+    std::vector<double> subT(b->n_snowpacks, 0.0);   // (zeros where the caller gives no substrate temperature)
     for (int s = 0; s < b->n_snowpacks && b->substrate_temperature; ++s) subT[s] = b->substrate_temperature[s];
-    smrt_host::gauss_legendre_positive(NM, gl.data(), nullptr);
-    SoBatch d{};
-    d.S = b->n_snowpacks; d.Lmax = L; d.F = b->n_frequencies; d.n_theta = b->n_theta;
-    d.emmodel = b->emmodel; d.micro = b->microstructure; d.sub_kind = b->substrate_kind; d.nmax = NM;
-    d.n_iter = n_iter; d.rj = b->rayleigh_jeans ? 1 : 0; d.nsamp = azimuth_samples(b->m_max); d.rtol = rtol;
-    d.n_pairs = N; d.chunk_begin = 0; d.chunk_count = N;
-    d.n_layers = nl.data();
-    d.thickness = b->thickness; d.frac_volume = b->frac_volume; d.temperature = b->temperature;
-    d.p1 = b->micro_p1; d.p2 = b->micro_p2; d.frequency = b->frequency; d.theta = b->theta; d.liquid_water = b->liquid_water;
-    d.layer_kind = b->layer_kind ? kinds.data() : nullptr;
-    d.sub_p1 = b->substrate_p1; d.sub_p2 = b->substrate_p2; d.sub_T = subT.data(); d.gl_mu = gl.data();
+    smrt_host::gauss_legendre_positive(d.nmax, gl.data(), nullptr);
+    d.chunk_begin = 0; d.chunk_count = N;
+    d.theta = b->theta; d.sub_T = subT.data(); d.gl_mu = gl.data();
     d.stage = stage.data(); d.nsub = nsub.data(); d.nstream = nstream.data(); d.vec = vec.data(); d.srcterm = srcterm.data();
     d.out = out; d.status = status; d.layer_out = layer_out; d.streams = streams; d.maxrad = max_radiance; d.orders = orders;
     for (long long i = 0; i < N; ++i)
         for (int l = 0; l < L; ++l) so_layer_item(d, i, l);
-    std::vector<long long> ws_off((size_t)N);
+    std::vector<long long> ws_off(n.ws_off);
     long long total = 0;
     for (long long i = 0; i < N; ++i) {
         long long n_sub = 0, n_lay = 0;
@@ -48,7 +41,7 @@ int32_t smrt_successive_order_host_run(const smrt_batch* b, int32_t n_iter, doub
         ws_off[(size_t)i] = total;
         total += (2 * n_sub + n_lay) * Dp + 2 * n_lay * Dh;
     }
-    std::vector<double> wt((size_t)N * L * Dp * Dp, 0.0), ws((size_t)total, 0.0), lds((size_t)so_lds_doubles(NM, b->n_theta), 0.0);
+    std::vector<double> wt((size_t)N * n.wt_pair, 0.0), ws((size_t)total, 0.0), lds(n.lds_sweep / sizeof(double), 0.0);
     d.wt = wt.data(); d.ws = ws.data(); d.ws_off = ws_off.data();
     for (long long i = 0; i < N; ++i)
         for (int l = 0; l < L; ++l) emu::run_block(kSoThreads, order, [&] { so_prep_item<kSoThreads>(d, i, l); });

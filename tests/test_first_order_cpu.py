@@ -7,7 +7,6 @@ against the reference); the contributions and backscatter_layer on that same sca
 ka 1e-10 relative (tests/test_gpu_parity.py)."""
 import ctypes as C
 import os
-import subprocess
 import types
 
 import numpy as np
@@ -15,6 +14,7 @@ import pytest
 
 import smrt_amd
 from first_order_restatement import CASES, CONTRIBUTIONS, SIGMA_RTOL, build_snowpack, solve_case
+from host_build import host_library
 from smrt_amd import make_model, sensor_list
 from smrt_amd import _native
 from smrt_amd.core.error import SMRTError
@@ -22,8 +22,6 @@ from smrt_amd.inputs.make_medium import make_interface, make_snowpack, make_soil
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GOLDEN = os.path.join(ROOT, "tests", "golden")
-EMU_DIR = os.path.join(ROOT, "tests", "hostemu")
-HOST_LIB = os.path.join(EMU_DIR, "libsmrt_first_order_host.so")
 
 
 def api():
@@ -176,13 +174,7 @@ def test_fixtures_exercise_every_mechanism():
 # ---- the device arithmetic on the CPU ----------------------------------------------------------------------------------
 @pytest.fixture(scope="module")
 def host_run():
-    csrc = os.path.join(ROOT, "smrt_amd", "csrc")
-    srcs = [os.path.join(EMU_DIR, "first_order_host.cpp"), os.path.join(EMU_DIR, "emu_runtime.hpp"),
-            os.path.join(ROOT, "include", "smrt_dort.h")] + [os.path.join(csrc, f) for f in
-                                                             ("first_order_kernel.hpp", "dort_physics.hpp", "dort_layout.hpp", "spmd.hpp")]
-    if not os.path.exists(HOST_LIB) or any(os.path.getmtime(s) > os.path.getmtime(HOST_LIB) for s in srcs):
-        subprocess.check_call(["g++", "-O2", "-std=c++17", "-shared", "-fPIC", "-DSMRT_HOST_EMU", "-I", EMU_DIR, "-o", HOST_LIB, srcs[0]])
-    lib = C.CDLL(HOST_LIB)
+    lib = host_library("libsmrt_first_order_host.so", "first_order_host.cpp")
     P = C.POINTER
     lib.smrt_first_order_host_run.argtypes = [P(_native.SmrtBatch), P(_native.FirstOrderExtras), P(C.c_int64), C.c_int64, P(C.c_double),
                                               P(C.c_int32), P(C.c_double), P(C.c_double), P(C.c_double)]

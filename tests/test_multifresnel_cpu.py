@@ -7,7 +7,6 @@ Tolerances: 1e-6 K for every brightness temperature (TB_ATOL, the project's bar)
 relative (tests/test_gpu_parity.py); layers_used exactly; tau_snowpack 1e-12 relative.  Measured: profiles/multifresnel_parity.txt."""
 import ctypes as C
 import os
-import subprocess
 import threading
 import types
 import warnings
@@ -15,6 +14,7 @@ import warnings
 import numpy as np
 import pytest
 
+from host_build import host_library
 from smrt_amd import _native, make_model, sensor_list
 from smrt_amd.core.error import SMRTError, SMRTWarning
 from smrt_amd.inputs.make_medium import make_interface, make_snowpack, make_soil
@@ -22,8 +22,6 @@ from multifresnel_restatement import CASES, TB_ATOL, build_snowpack, case_by_nam
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GOLDEN = os.path.join(ROOT, "tests", "golden")
-EMU_DIR = os.path.join(ROOT, "tests", "hostemu")
-HOST_LIB = os.path.join(EMU_DIR, "libsmrt_multifresnel_host.so")
 IDS = dict(ids=lambda c: c["name"])
 
 
@@ -86,13 +84,7 @@ def test_fixtures_cover_what_they_can():
 # ---- the device source on the CPU ---------------------------------------------------------------------------------------
 @pytest.fixture(scope="module")
 def host_lib():
-    csrc = os.path.join(ROOT, "smrt_amd", "csrc")
-    sources = [os.path.join(EMU_DIR, "multifresnel_host.cpp"), os.path.join(ROOT, "include", "smrt_dort.h")]
-    sources += [os.path.join(csrc, f) for f in ("multifresnel_kernel.hpp", "dort_physics.hpp", "dort_layout.hpp", "spmd.hpp")]
-    if not os.path.exists(HOST_LIB) or any(os.path.getmtime(s) > os.path.getmtime(HOST_LIB) for s in sources):
-        subprocess.check_call(["g++", "-O2", "-std=c++17", "-shared", "-fPIC", "-DSMRT_HOST_EMU", "-I", EMU_DIR, "-o", HOST_LIB,
-                               sources[0]], cwd=ROOT)
-    lib = C.CDLL(HOST_LIB)
+    lib = host_library("libsmrt_multifresnel_host.so", "multifresnel_host.cpp")
     lib.smrt_multifresnel_host_run.restype = C.c_int32
     return lib
 

@@ -8,13 +8,13 @@ ke 1e-10, backward scattering 1e-10 relative (tests/test_gpu_parity.py's bars fo
 relative.  Measured: profiles/nadir_lrm_altimetry_parity.txt."""
 import ctypes as C
 import os
-import subprocess
 import threading
 import types
 
 import numpy as np
 import pytest
 
+from host_build import host_library
 from smrt_amd import _native, make_model
 from smrt_amd.core.error import SMRTError
 from smrt_amd.core.result import AltimetryResult, open_result
@@ -24,8 +24,6 @@ from nadir_lrm_altimetry_restatement import CASES, REL_BAR, SMALL, build_snowpac
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GOLDEN = os.path.join(ROOT, "tests", "golden")
-EMU_DIR = os.path.join(ROOT, "tests", "hostemu")
-HOST_LIB = os.path.join(EMU_DIR, "libsmrt_lrm_host.so")
 IDS = dict(ids=lambda c: c["name"])
 API = types.SimpleNamespace(make_snowpack=make_snowpack, make_soil=make_soil, make_interface=make_interface,
                             lrm_altimeter_list=lrm_altimeter_list)
@@ -111,14 +109,7 @@ def test_fixtures_cover_what_they_must():
 # ---- the device source on the CPU ---------------------------------------------------------------------------------------
 @pytest.fixture(scope="module")
 def host_lib():
-    csrc = os.path.join(ROOT, "smrt_amd", "csrc")
-    sources = [os.path.join(EMU_DIR, "nadir_lrm_altimetry_host.cpp"), os.path.join(ROOT, "include", "smrt_dort.h")]
-    sources += [os.path.join(csrc, f) for f in ("nadir_lrm_altimetry_kernel.hpp", "first_order_kernel.hpp", "dort_physics.hpp",
-                                                 "dort_layout.hpp", "spmd.hpp")]
-    if not os.path.exists(HOST_LIB) or any(os.path.getmtime(s) > os.path.getmtime(HOST_LIB) for s in sources):
-        subprocess.check_call(["g++", "-O2", "-std=c++17", "-shared", "-fPIC", "-DSMRT_HOST_EMU", "-I", EMU_DIR, "-o", HOST_LIB,
-                               sources[0]], cwd=ROOT)
-    lib = C.CDLL(HOST_LIB)
+    lib = host_library("libsmrt_lrm_host.so", "nadir_lrm_altimetry_host.cpp")
     lib.smrt_lrm_host_run.restype = C.c_int32
     lib.smrt_lrm_host_layers.restype = C.c_int32
     lib.smrt_lrm_host_i0.restype = C.c_double

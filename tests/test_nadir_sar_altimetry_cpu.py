@@ -7,13 +7,13 @@ Bars: every sample of every contribution within 1e-8 x the largest value of the 
 frequency and Doppler bin 1e-12 relative; f0 and f1 1e-10 absolute.  Measured: profiles/nadir_sar_altimetry_parity.txt."""
 import ctypes as C
 import os
-import subprocess
 import threading
 import types
 
 import numpy as np
 import pytest
 
+from host_build import host_library
 from smrt_amd import _native, make_model
 from smrt_amd.core.error import SMRTError
 from smrt_amd.core.result import AltimetryResult, open_result
@@ -25,7 +25,6 @@ from nadir_sar_altimetry_restatement import (CASES, REL_BAR, build_snowpack, cas
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GOLDEN = os.path.join(ROOT, "tests", "golden")
-EMU_DIR = os.path.join(ROOT, "tests", "hostemu")
 IDS = dict(ids=lambda c: c["name"])
 API = types.SimpleNamespace(make_snowpack=make_snowpack, make_soil=make_soil, make_interface=make_interface,
                             sar_altimeter_list=sar_altimeter_list, TerrainInfo=TerrainInfo)
@@ -124,24 +123,14 @@ def test_fixtures_cover_what_they_must():
 
 
 # ---- the device source on the CPU ---------------------------------------------------------------------------------------
-def _host_library(name, source, headers):
-    csrc = os.path.join(ROOT, "smrt_amd", "csrc")
-    lib = os.path.join(EMU_DIR, name)
-    sources = [os.path.join(EMU_DIR, source), os.path.join(ROOT, "include", "smrt_dort.h")] + [os.path.join(csrc, f) for f in headers]
-    if not os.path.exists(lib) or any(os.path.getmtime(s) > os.path.getmtime(lib) for s in sources):
-        subprocess.check_call(["g++", "-O2", "-std=c++17", "-shared", "-fPIC", "-DSMRT_HOST_EMU", "-I", EMU_DIR, "-o", lib, sources[0]], cwd=ROOT)
-    return C.CDLL(lib)
-
-
 @pytest.fixture(scope="module")
 def host_lib():
-    shared = ("nadir_lrm_altimetry_kernel.hpp", "first_order_kernel.hpp", "dort_physics.hpp", "dort_layout.hpp", "spmd.hpp")
-    lib = _host_library("libsmrt_sar_host.so", "nadir_sar_altimetry_host.cpp", ("nadir_sar_altimetry_kernel.hpp", "solver_refusals.hpp") + shared)
+    lib = host_library("libsmrt_sar_host.so", "nadir_sar_altimetry_host.cpp")
     lib.smrt_sar_host_run.restype = C.c_int32
     lib.smrt_sar_host_refusal.restype = C.c_char_p
     for f in (lib.smrt_sar_host_f0, lib.smrt_sar_host_f1):
         f.restype, f.argtypes = C.c_double, [C.c_double]
-    lib.layers = _host_library("libsmrt_lrm_host.so", "nadir_lrm_altimetry_host.cpp", shared)
+    lib.layers = host_library("libsmrt_lrm_host.so", "nadir_lrm_altimetry_host.cpp")
     lib.layers.smrt_lrm_host_layers.restype = C.c_int32
     return lib
 

@@ -22,9 +22,10 @@ from smrt_amd.core.terrain import TerrainInfo
 from smrt_amd.inputs import sar_altimeter_list
 from smrt_amd.inputs.make_medium import make_interface, make_snowpack, make_soil
 import nadir_sar_altimetry_restatement as dinardo
+from host_build import host_library
 from nadir_sar_altimetry_halimi14_restatement import (CASES, REL_BAR, build_snowpack, case_by_name, compensation_shifts, halimi14_table,
                                                       impulse_response, make_sensor, model_options, solve_case, solver_options)
-from test_nadir_sar_altimetry_cpu import (HostContext, _host_library, assert_axes, assert_close, assert_map, assert_vertical, map_of,
+from test_nadir_sar_altimetry_cpu import (HostContext, assert_axes, assert_close, assert_map, assert_vertical, map_of,
                                           host_lib as dinardo_host_lib)  # noqa: F401  (dinardo_host_lib is a fixture)
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -59,12 +60,10 @@ def assert_table(table, reference, what):
 # ---- the device source on the CPU, both models -----------------------------------------------------------------------------
 @pytest.fixture(scope="module")
 def host_lib():
-    shared = ("nadir_lrm_altimetry_kernel.hpp", "first_order_kernel.hpp", "dort_physics.hpp", "dort_layout.hpp", "spmd.hpp")
-    lib = _host_library("libsmrt_sar_halimi14_host.so", "nadir_sar_altimetry_halimi14_host.cpp",
-                        ("nadir_sar_altimetry_kernel.hpp", "solver_refusals.hpp") + shared)
+    lib = host_library("libsmrt_sar_halimi14_host.so", "nadir_sar_altimetry_halimi14_host.cpp")
     lib.smrt_sar_host_run.restype = lib.smrt_sar_host_run_table.restype = C.c_int32
     lib.smrt_sar_host_refusal.restype = C.c_char_p
-    lib.layers = _host_library("libsmrt_lrm_host.so", "nadir_lrm_altimetry_host.cpp", shared)
+    lib.layers = host_library("libsmrt_lrm_host.so", "nadir_lrm_altimetry_host.cpp")
     lib.layers.smrt_lrm_host_layers.restype = C.c_int32
     return lib
 

@@ -9,13 +9,13 @@ import ctypes as C
 import functools
 import os
 import re
-import subprocess
 import types
 
 import numpy as np
 import pytest
 
 import second_order_restatement as R
+from host_build import host_library
 from second_order_restatement import CASES, CONTRIBUTIONS, SIGMA_RTOL, build_snowpack, options_of, solve_case
 from smrt_amd import _native, make_model, sensor_list
 from smrt_amd.core.error import SMRTError
@@ -23,8 +23,6 @@ from smrt_amd.inputs.make_medium import make_interface, make_snowpack, make_soil
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GOLDEN = os.path.join(ROOT, "tests", "golden")
-EMU_DIR = os.path.join(ROOT, "tests", "hostemu")
-HOST_LIB = os.path.join(EMU_DIR, "libsmrt_second_order_host.so")
 IDS = [c["name"] for c in CASES]
 
 
@@ -215,14 +213,7 @@ def test_fixtures_pin_the_mechanisms_and_the_findings():
 @pytest.fixture(scope="module")
 def host_lib():
     """The device source (second_order_kernel.hpp and what it includes) compiled with g++: tests/hostemu/second_order_host.cpp."""
-    csrc = os.path.join(ROOT, "smrt_amd", "csrc")
-    srcs = [os.path.join(EMU_DIR, "second_order_host.cpp"), os.path.join(EMU_DIR, "emu_runtime.hpp"),
-            os.path.join(ROOT, "include", "smrt_dort.h")] + [os.path.join(csrc, f) for f in (
-                "second_order_kernel.hpp", "first_order_kernel.hpp", "dort_phase_kernel.hpp", "dort_physics.hpp", "dort_layout.hpp",
-                "dort_host_common.hpp", "spmd.hpp")]
-    if not os.path.exists(HOST_LIB) or any(os.path.getmtime(s) > os.path.getmtime(HOST_LIB) for s in srcs):
-        subprocess.check_call(["g++", "-O2", "-std=c++17", "-shared", "-fPIC", "-DSMRT_HOST_EMU", "-I", EMU_DIR, "-o", HOST_LIB, srcs[0]])
-    lib = C.CDLL(HOST_LIB)
+    lib = host_library("libsmrt_second_order_host.so", "second_order_host.cpp")
     P = C.POINTER
     lib.smrt_second_order_host_run.argtypes = [P(_native.SmrtBatch), P(_native.SecondOrderExtras), C.c_int32, P(C.c_double), P(C.c_int32),
                                                P(C.c_double), P(C.c_double), P(C.c_double)]

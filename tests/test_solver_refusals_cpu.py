@@ -3,17 +3,12 @@ they share in dort_host_common.hpp), compiled with g++ and reached without a GPU
 one valid batch of the smallest shape, broken one field at a time, and the exact message every solver has always answered
 with."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
-from conftest import ROOT
+from host_build import host_library
 from smrt_amd._native import PackedBatch, SmrtBatch
-
-EMU_DIR = os.path.join(ROOT, "tests", "hostemu")
-HOST_LIB = os.path.join(EMU_DIR, "libsmrt_solver_refusals_host.so")
 
 FO, SO2, SO, SOA, MF, LRM = range(6)
 NAMES = ["first_order", "second_order", "successive_order", "successive_order_active", "multifresnel", "nadir_lrm_altimetry"]
@@ -31,13 +26,7 @@ SOA_RAYLEIGH = "the Rayleigh-family emmodels have azimuth modes 0 to 2 only: m_m
 
 @pytest.fixture(scope="module")
 def refusal():
-    csrc = os.path.join(ROOT, "smrt_amd", "csrc")
-    sources = [os.path.join(EMU_DIR, "solver_refusals_host.cpp"), os.path.join(EMU_DIR, "emu_runtime.hpp"),
-               os.path.join(ROOT, "include", "smrt_dort.h")] + sorted(os.path.join(csrc, f) for f in os.listdir(csrc) if f.endswith(".hpp"))
-    if not os.path.exists(HOST_LIB) or any(os.path.getmtime(s) > os.path.getmtime(HOST_LIB) for s in sources):
-        subprocess.check_call(["g++", "-O2", "-std=c++17", "-shared", "-fPIC", "-DSMRT_HOST_EMU", "-I", EMU_DIR, "-o", HOST_LIB,
-                               sources[0]], cwd=ROOT)
-    fn = C.CDLL(HOST_LIB).smrt_emu_solver_refusal
+    fn = host_library("libsmrt_solver_refusals_host.so", "solver_refusals_host.cpp").smrt_emu_solver_refusal
     fn.argtypes = [C.c_int, C.POINTER(SmrtBatch), C.c_int, C.c_double, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
                    C.POINTER(C.c_int64), C.c_int64]
     fn.restype = C.c_char_p

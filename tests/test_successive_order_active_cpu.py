@@ -8,7 +8,6 @@ the fixture -- the project's active-mode contract (profiles/first_order_parity.t
 reference has them; layer scalars: eps 1e-12, ks 1e-11, ka 1e-10 relative (tests/test_gpu_parity.py)."""
 import ctypes as C
 import os
-import subprocess
 import sys
 import threading
 import types
@@ -16,6 +15,7 @@ import types
 import numpy as np
 import pytest
 
+from host_build import host_library
 from smrt_amd import _native, make_model, sensor_list
 from smrt_amd.core.error import SMRTError
 from smrt_amd.inputs.make_medium import make_interface, make_snowpack, make_soil
@@ -24,8 +24,6 @@ from successive_order_active_restatement import (CASES, build_snowpack, case_by_
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GOLDEN = os.path.join(ROOT, "tests", "golden")
-EMU_DIR = os.path.join(ROOT, "tests", "hostemu")
-HOST_LIB = os.path.join(EMU_DIR, "libsmrt_so_active_host.so")
 
 
 def api():
@@ -114,14 +112,7 @@ def test_tolerance_identity():
 # ---- the device source on the CPU ---------------------------------------------------------------------------------------
 @pytest.fixture(scope="module")
 def host_lib():
-    sources = [os.path.join(EMU_DIR, "successive_order_active_host.cpp"), os.path.join(EMU_DIR, "emu_runtime.hpp"),
-               os.path.join(ROOT, "include", "smrt_dort.h")]
-    csrc = os.path.join(ROOT, "smrt_amd", "csrc")
-    sources += [os.path.join(csrc, f) for f in sorted(os.listdir(csrc)) if f.endswith(".hpp")]
-    if not os.path.exists(HOST_LIB) or any(os.path.getmtime(s) > os.path.getmtime(HOST_LIB) for s in sources):
-        subprocess.check_call(["g++", "-O2", "-std=c++17", "-shared", "-fPIC", "-DSMRT_HOST_EMU", "-I", EMU_DIR, "-o", HOST_LIB,
-                               sources[0]], cwd=ROOT)
-    lib = C.CDLL(HOST_LIB)
+    lib = host_library("libsmrt_so_active_host.so", "successive_order_active_host.cpp")
     lib.smrt_so_active_host_run.restype = C.c_int32
     lib.smrt_so_active_host_incident.restype = C.c_int32
     return lib

@@ -8,7 +8,6 @@ package's bar of 1e-6 K keeps its margin for the device); device source against 
 project's bar for a brightness temperature); layer scalars: eps 1e-12, ks 1e-11, ka 1e-10 relative (tests/test_gpu_parity.py)."""
 import ctypes as C
 import os
-import subprocess
 import sys
 import threading
 import types
@@ -17,6 +16,7 @@ import numpy as np
 import pytest
 
 import smrt_amd
+from host_build import host_library
 from smrt_amd import _native, make_model, sensor_list
 from smrt_amd.core.error import SMRTError
 from smrt_amd.inputs.make_medium import make_interface, make_snowpack, make_soil
@@ -25,8 +25,6 @@ from successive_order_restatement import (CASES, FIXTURE_CASES, SUBSTRATE_CASES,
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GOLDEN = os.path.join(ROOT, "tests", "golden")
-EMU_DIR = os.path.join(ROOT, "tests", "hostemu")
-HOST_LIB = os.path.join(EMU_DIR, "libsmrt_successive_order_host.so")
 
 
 def api():
@@ -83,15 +81,7 @@ def test_fixtures_cover_what_they_must():
 # ---- the device source on the CPU ---------------------------------------------------------------------------------------
 @pytest.fixture(scope="module")
 def host_lib():
-    sources = [os.path.join(EMU_DIR, "successive_order_host.cpp"), os.path.join(EMU_DIR, "emu_runtime.hpp"),
-               os.path.join(ROOT, "include", "smrt_dort.h")]
-    csrc = os.path.join(ROOT, "smrt_amd", "csrc")
-    sources += [os.path.join(csrc, f) for f in ("successive_order_kernel.hpp", "dort_phase_kernel.hpp", "dort_physics.hpp",
-                                                "dort_layout.hpp", "spmd.hpp", "dort_host_common.hpp")]
-    if not os.path.exists(HOST_LIB) or any(os.path.getmtime(s) > os.path.getmtime(HOST_LIB) for s in sources):
-        subprocess.check_call(["g++", "-O2", "-std=c++17", "-shared", "-fPIC", "-DSMRT_HOST_EMU", "-I", EMU_DIR, "-o", HOST_LIB,
-                               sources[0]], cwd=ROOT)
-    lib = C.CDLL(HOST_LIB)
+    lib = host_library("libsmrt_successive_order_host.so", "successive_order_host.cpp")
     lib.smrt_successive_order_host_run.restype = C.c_int32
     return lib
 
