@@ -338,6 +338,13 @@ int32_t smrt_dort_kernel_breakdown(smrt_dort_ctx* ctx, int32_t enable, double* m
  * the environment variable SMRT_DORT_EIG=0 / 1 overrides it for experiments).  Takes effect at the next upload. */
 int32_t smrt_dort_set_diagonalisation(smrt_dort_ctx* ctx, int32_t mode);
 
+/* The prep stage of the LDS-resident passive pipelines (streams x polarisations <= 64).  mode: SMRT_PREP_PER_PAIR (one
+ * workgroup per pair works through its layers, LDS sized for the largest layer the batch may have), SMRT_PREP_PER_LAYER (a pair
+ * setup kernel, then one workgroup per (pair, layer) item in one launch per size class of rows; the staging area it leaves is
+ * bitwise the same), or -1: the default (the environment variable SMRT_DORT_PREP_LAYERS=0 / 1 overrides it for experiments).
+ * Other batches keep their prep kernels.  Takes effect at the next upload. */
+int32_t smrt_dort_set_prep(smrt_dort_ctx* ctx, int32_t mode);
+
 /* What the uploaded batch runs on, as numbers (tests assert the designed kernel choice with these instead of wall-clock
  * ratios): info[SMRT_INFO_*], at most n entries written; returns SMRT_INFO_COUNT, -1 on error.
  *   PIPELINE      SMRT_PIPELINE_*: the kernels a launch of this batch consists of
@@ -350,9 +357,12 @@ int32_t smrt_dort_set_diagonalisation(smrt_dort_ctx* ctx, int32_t mode);
  *   RAYLEIGH_CLOSED_FORM  1: the layers with a Rayleigh phase matrix (dmrt_qca_shortrange, dmrt_qcacp_shortrange,
  *                 nonscattering, rayleigh-family host emmodels) of this batch skip Cholesky and the iteration: their azimuth
  *                 mode 0 is "diagonal minus rank two" and is diagonalised in closed form (passive batches on the strip finish
- *                 kernels; SMRT_DORT_RAYLEIGH=0 switches it off for experiments) */
+ *                 kernels; SMRT_DORT_RAYLEIGH=0 switches it off for experiments)
+ *   PREP          SMRT_PREP_*: the prep stage of this batch (PER_LAYER only on the LDS pipelines in passive mode) */
 enum { SMRT_INFO_PIPELINE = 0, SMRT_INFO_CHUNK_PAIRS, SMRT_INFO_CHUNKS, SMRT_INFO_PRUNE_ROUNDS, SMRT_INFO_STAGED_ITEMS,
-       SMRT_INFO_BLOCK_THREADS, SMRT_INFO_N_MAX, SMRT_INFO_DIAGONALISATION, SMRT_INFO_RAYLEIGH_CLOSED_FORM, SMRT_INFO_COUNT };
+       SMRT_INFO_BLOCK_THREADS, SMRT_INFO_N_MAX, SMRT_INFO_DIAGONALISATION, SMRT_INFO_RAYLEIGH_CLOSED_FORM, SMRT_INFO_PREP,
+       SMRT_INFO_COUNT };
+enum { SMRT_PREP_PER_PAIR = 0, SMRT_PREP_PER_LAYER = 1 };
 enum { SMRT_DIAG_JACOBI = 0,      /* one-sided Jacobi on B = L+^T L- (singular values to high relative accuracy) */
        SMRT_DIAG_SYMMETRIC = 1 }; /* Householder tridiagonalisation + implicit QL on S = B B^T (passive, N <= 64: the default) */
 enum { SMRT_PIPELINE_FUSED = 0,          /* one kernel per pair, matrices in LDS (N <= 64) */

@@ -31,7 +31,7 @@ struct smrt_dort_ctx {
     hipStream_t stream = nullptr;
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     std::string err;
-    DevBuf d_nl, d_thick, d_fv, d_temp, d_p1, d_p2, d_freq, d_theta, d_gl, d_out, d_status, d_layer, d_stream, d_n3, d_stage, d_work, d_stL, d_stB, d_std, d_sts, d_stn, d_sti, d_sub1, d_sub2, d_subT, d_atm, d_pairmap, d_kind, d_phase, d_done, d_hostlayer, d_hostcoeff, d_hoststreams, d_hostphase, d_dispatch, d_regws, d_itfslot, d_itf, d_itfcoh, d_lw, d_ste, d_strot;
+    DevBuf d_nl, d_thick, d_fv, d_temp, d_p1, d_p2, d_freq, d_theta, d_gl, d_out, d_status, d_layer, d_stream, d_n3, d_stage, d_work, d_stL, d_stB, d_std, d_sts, d_stn, d_sti, d_sub1, d_sub2, d_subT, d_atm, d_pairmap, d_kind, d_phase, d_done, d_hostlayer, d_hostcoeff, d_hoststreams, d_hostphase, d_dispatch, d_regws, d_itfslot, d_itf, d_itfcoh, d_lw, d_ste, d_strot, d_strec;
     smrt::DevBatch dev{};
     bool uploaded = false;
     int out_stride = 0;
@@ -41,6 +41,8 @@ struct smrt_dort_ctx {
     size_t finish2_lds_bytes = 0;
     size_t finish_reg_lds_bytes = 0;
     size_t prep_wide_lds_bytes = 0;
+    int prep_mode = -1;         // smrt_dort_set_prep: -1 default, 0 one workgroup per pair, 1 per (pair, layer) item where built
+    bool prep_layers = false;   // this batch: the per-layer prep (k_prep_layer.hip) in place of dort_prep_kernel
     bool prep_wide = false;     // 64 < N <= 128, passive: the LDS-resident prep kernel (packed triangles) with eight wavefronts
     size_t finish_strip_lds_bytes = 0, finish_strip4_lds_bytes = 0;
     bool finish_strip4 = false; // ... its four-wavefront instance on the LDS pipeline (N <= 64) instead of the register-resident kernel
@@ -111,6 +113,9 @@ hipError_t prep(smrt_dort_ctx* ctx, const smrt::DevBatch& c, int nt);
 hipError_t prep_wide(smrt_dort_ctx* ctx, const smrt::DevBatch& c);   // the same for 64 < N <= 128: 512 threads, one workgroup per CU
 hipError_t finish(smrt_dort_ctx* ctx, const smrt::DevBatch& c, int nt, bool two_slot);
 void occupancy_report(smrt_dort_ctx* ctx, int nt);
+// k_prep_layer.hip: the per-layer prep of the same pipelines -- pair setup, then one layer kernel launch per size class of rows
+// over the `items` (pair, layer) items of the round
+hipError_t prep_layers(smrt_dort_ctx* ctx, const smrt::DevBatch& c, long long items);
 // k_finish_reg.hip: the register-resident finish kernel of the same pipeline, one wavefront per pair
 hipError_t finish_reg(smrt_dort_ctx* ctx, const smrt::DevBatch& c);
 // k_finish_strip.hip: the strip finish kernel of the 64 < N <= 128 pipeline (passive), one workgroup of eight wavefronts per pair

@@ -382,7 +382,9 @@ SMRT_DEV void tile_foreach(int ti, int tj, int N, F f) {
 // column index (beta ~ ke / mu, mu descending); the one-sided Jacobi converges in fewer sweeps when the large
 // columns come first (de Rijk), and nothing downstream depends on the order of the eigenpairs.
 template <int NT, bool PK = false>   // PK: Lp and Lm in packed lower storage (C is always a full matrix)
-SMRT_DEV void lt_times_l_mfma(const double* Lp, const double* Lm, double* C, int N, int LD, bool reverse_cols = false) {
+SMRT_DEV void lt_times_l_mfma(const double* Lp, const double* Lm, double* C, int N, int LD, bool reverse_cols = false,
+                              int LDC = 0 /* leading dimension of C where it is not LD (packed operands of another order) */) {
+    const int ldc = LDC ? LDC : LD;
     const int wave = tid() / SMRT_LANES;
     constexpr int NW = NT / SMRT_LANES;
     const int RT = (N + 15) >> 4;
@@ -402,7 +404,7 @@ SMRT_DEV void lt_times_l_mfma(const double* Lp, const double* Lm, double* C, int
             const bool kin = k < N;
             mfma_f64_16x16x4((kin && k >= i) ? av : 0.0, (kin && k >= j) ? bv : 0.0, c);   // (k >= i, k < N imply i < N)
         }
-        tile_foreach(ti, tj, N, [&](int reg, int row, int col) { C[(reverse_cols ? N - 1 - col : col) * LD + row] = c[reg]; });
+        tile_foreach(ti, tj, N, [&](int reg, int row, int col) { C[(reverse_cols ? N - 1 - col : col) * ldc + row] = c[reg]; });
     }
     block_sync();
 }

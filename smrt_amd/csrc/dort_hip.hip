@@ -49,6 +49,9 @@ static DevBatch chunk_of(const smrt_dort_ctx* ctx, const DevBatch& d, long long 
 #ifndef SMRT_DORT_LANES_DEFAULT
 #define SMRT_DORT_LANES_DEFAULT 1   // concurrent pipeline passes on the LDS pipelines (SMRT_DORT_LANES overrides; measured in profiles/)
 #endif
+#ifndef SMRT_PREP_DEFAULT
+#define SMRT_PREP_DEFAULT SMRT_PREP_PER_LAYER   // the prep of the passive LDS pipelines (smrt_dort_set_prep / SMRT_DORT_PREP_LAYERS override)
+#endif
 #ifndef SMRT_FINISH_STRIP_DEFAULT
 #define SMRT_FINISH_STRIP_DEFAULT 1   // the strip finish kernel where it is supported (64 < N <= 128, passive; set_pipeline(4) / SMRT_DORT_FINISH_STRIP=0: the pivoted one)
 #endif
@@ -63,6 +66,7 @@ static hipError_t launch_pipeline(smrt_dort_ctx* ctx, const DevBatch& d) {
     // removed layers must read "nothing staged")
     const int rounds = (d.prune_tau > 0.0 && !d.coherent && getenv("SMRT_DORT_NO_PRUNE_ROUNDS") == nullptr) ? std::min(4, d.Lmax) : 1;
     auto prep = [&](const DevBatch& c, unsigned grid) {
+        if (ctx->prep_layers) return smrt_launch::prep_layers(ctx, c, c.pair_count * (c.layer_hi - c.layer_lo));
         if (ctx->big) return smrt_launch::prep_gmem_big(ctx, c, grid, ctx->active, ctx->nmax_rows <= 256 ? 4 : 6);
         if (ctx->prep_wide) return smrt_launch::prep_wide(ctx, c);
         if (ctx->gmem_split) return smrt_launch::prep_gmem(ctx, c, grid, ctx->active);
@@ -124,6 +128,7 @@ static hipError_t launch_pipeline(smrt_dort_ctx* ctx, const DevBatch& d) {
             ctx->stage.d = stage0.d + it0 * stage0.vec_stride; ctx->stage.sigma = stage0.sigma + it0 * stage0.vec_stride;
             ctx->stage.n = stage0.n + it0; ctx->stage.Linv = stage0.Linv + it0 * stage0.linv_stride;
             if (stage0.eig_rot) { ctx->stage.eig_e = stage0.eig_e + it0 * 2 * stage0.vec_stride; ctx->stage.eig_rot = stage0.eig_rot + it0 * stage0.rot_stride; }
+            if (stage0.rec) ctx->stage.rec = stage0.rec + it0 * stage0.rec_stride;
             if (stage0.ws) ctx->stage.ws = stage0.ws + (long long)lane * ctx->chunk_pairs * rg::kSlotDoubles;
         }
         if (rounds > 1 || d.coherent) {   // unprocessed layers must read as "nothing staged", pairs as "not cut yet"
@@ -200,7 +205,7 @@ void smrt_dort_destroy(smrt_dort_ctx* ctx) {
     (void)hipSetDevice(ctx->device);
     DevBuf* bufs[] = {&ctx->d_nl, &ctx->d_thick, &ctx->d_fv, &ctx->d_temp, &ctx->d_p1, &ctx->d_p2, &ctx->d_freq,
                       &ctx->d_theta, &ctx->d_gl, &ctx->d_out, &ctx->d_status, &ctx->d_layer, &ctx->d_stream, &ctx->d_n3, &ctx->d_stage, &ctx->d_work,
-                      &ctx->d_stL, &ctx->d_stB, &ctx->d_std, &ctx->d_sts, &ctx->d_stn, &ctx->d_sti, &ctx->d_ste, &ctx->d_strot, &ctx->d_regws, &ctx->d_itfslot, &ctx->d_itf, &ctx->d_itfcoh,
+                      &ctx->d_stL, &ctx->d_stB, &ctx->d_std, &ctx->d_sts, &ctx->d_stn, &ctx->d_sti, &ctx->d_ste, &ctx->d_strot, &ctx->d_strec, &ctx->d_regws, &ctx->d_itfslot, &ctx->d_itf, &ctx->d_itfcoh,
                       &ctx->d_sub1, &ctx->d_sub2, &ctx->d_subT, &ctx->d_atm, &ctx->d_pairmap, &ctx->d_kind, &ctx->d_hostlayer, &ctx->d_hoststreams, &ctx->d_hostphase, &ctx->d_dispatch, &ctx->d_phase, &ctx->d_done, &ctx->d_lw, &ctx->d_gather_out, &ctx->d_gather_status,
                       &ctx->d_scalar};
     for (DevBuf* b : bufs) b->release();
@@ -239,6 +244,14 @@ int32_t smrt_dort_set_diagonalisation(smrt_dort_ctx* ctx, int32_t mode) {
     if (!ctx) return -1;
     if (mode < -1 || mode > SMRT_DIAG_SYMMETRIC) { ctx->err = "unknown diagonalisation mode"; return -1; }
     ctx->diag_mode = mode;
+    ctx->uploaded = false;  // the staging area is sized at upload time
+    return 0;
+}
+
+int32_t smrt_dort_set_prep(smrt_dort_ctx* ctx, int32_t mode) {
+    if (!ctx) return -1;
+    if (mode < -1 || mode > SMRT_PREP_PER_LAYER) { ctx->err = "unknown prep mode"; return -1; }
+    ctx->prep_mode = mode;
     ctx->uploaded = false;  // the staging area is sized at upload time
     return 0;
 }
@@ -319,6 +332,14 @@ static int32_t upload_impl(smrt_dort_ctx* ctx, const smrt_batch* b, int64_t pair
     ctx->nmax_rows = plan.NMAX;
     ctx->chunk_pairs = 0;
     ctx->eig = false;
+    // the per-layer prep (k_prep_layer.hip) in place of the per-pair prep kernel: the LDS pipelines in passive mode
+    // (smrt_dort_set_prep / SMRT_DORT_PREP_LAYERS select; its item records count in the staging budget below)
+    {
+        int want = ctx->prep_mode < 0 ? SMRT_PREP_DEFAULT : ctx->prep_mode;
+        if (const char* e = getenv("SMRT_DORT_PREP_LAYERS")) want = atoi(e) ? SMRT_PREP_PER_LAYER : SMRT_PREP_PER_PAIR;
+        ctx->prep_layers = !ctx->gmem_path && ctx->split && !ctx->active && plan.NMAX <= 64 && want == SMRT_PREP_PER_LAYER;
+    }
+    const size_t rec_doubles = ctx->prep_layers ? (size_t)prep_record_doubles(b->n_max_stream) : 0;
     // N > 128: the pipeline with the blocked Jacobi kernel (matrix in the staging area, column blocks through LDS)
     int big_min = 128;   // SMRT_DORT_BIG_MIN_N: experiments with the big pipeline on smaller matrices
     if (const char* e = getenv("SMRT_DORT_BIG_MIN_N")) big_min = std::max(64, atoi(e));
@@ -339,7 +360,7 @@ static int32_t upload_impl(smrt_dort_ctx* ctx, const smrt_batch* b, int64_t pair
         const size_t nmodes = ctx->active ? (size_t)b->m_max + 1 : 1;   // staging items per layer
         const size_t mat = (size_t)plan.NMAX * plan.LD;
         const int linv_stride = (plan.NMAX > 64) ? 2048 : 1024;   // inverses of the diagonal blocks of L+: four or eight of 256 doubles
-        const size_t per_pair = nmodes * b->n_layers_max * ((2 * mat + 2 * plan.NMAX + linv_stride) * sizeof(double) + sizeof(int));
+        const size_t per_pair = nmodes * b->n_layers_max * ((2 * mat + 2 * plan.NMAX + linv_stride + rec_doubles) * sizeof(double) + sizeof(int));
         // staging budget: 12 GB, or -- for the large matrices of the big pipeline, where 12 GB hold too few pairs to fill
         // the chip -- up to 60 % of the free device memory
         double budget = 12.0e9;
@@ -401,6 +422,11 @@ static int32_t upload_impl(smrt_dort_ctx* ctx, const smrt_batch* b, int64_t pair
         ctx->stage.n = (int*)ctx->d_stn.p; ctx->stage.Linv = ctx->big ? nullptr : (double*)ctx->d_sti.p;
         ctx->stage.linv_stride = linv_stride;
         ctx->stage.mat_stride = (long long)mat; ctx->stage.vec_stride = plan.NMAX;
+        ctx->stage.rec = nullptr; ctx->stage.rec_stride = (int)rec_doubles;
+        if (ctx->prep_layers) {
+            HIPCHK(ctx->d_strec.reserve(items * rec_doubles * sizeof(double)));
+            ctx->stage.rec = (double*)ctx->d_strec.p;
+        }
         // the symmetric eigensolver in place of the Jacobi kernel (N <= 64: the LDS pipelines): its tridiagonal forms and
         // rotation lists (not counted in the staging budget above: 148 KB per item at N = 64 on top of the 67 KB of L+ and B)
         {
@@ -802,6 +828,7 @@ int32_t smrt_dort_launch_info(smrt_dort_ctx* ctx, int64_t* info, int32_t n) {
     v[SMRT_INFO_N_MAX] = ctx->nmax_rows;
     v[SMRT_INFO_DIAGONALISATION] = (three && ctx->eig) ? SMRT_DIAG_SYMMETRIC : SMRT_DIAG_JACOBI;
     v[SMRT_INFO_RAYLEIGH_CLOSED_FORM] = (three && d.rayleigh_direct) ? 1 : 0;
+    v[SMRT_INFO_PREP] = (lds_pipeline && ctx->prep_layers) ? SMRT_PREP_PER_LAYER : SMRT_PREP_PER_PAIR;
     for (int k = 0; k < n && k < SMRT_INFO_COUNT; ++k) info[k] = v[k];
     return SMRT_INFO_COUNT;
 }

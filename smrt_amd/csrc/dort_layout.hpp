@@ -95,7 +95,14 @@ struct DevStage {
     double* eig_e;         // [item][2 * vec_stride] off-diagonal of the tridiagonal form (+ the scale), then the tau of the reflectors
     double* eig_rot;       // [item][rot_stride] the plane rotations of the QL iterations
     long long rot_stride;
+    // the per-layer prep kernels (dort_prep_layer.hpp): one record per item, written by the pair setup kernel, or null
+    double* rec;           // [item][rec_stride] kPrepRec* scalars, then the layer's stream cosines and weights
+    int rec_stride;        // prep_record_doubles(n_max_stream)
 };
+
+// record of one (pair, layer) item: what the layer kernel of the per-layer prep needs from the pair's setup
+enum { kPrepRecN = 0 /* streams */, kPrepRecKe, kPrepRecKs, kPrepRecPa, kPrepRecPb, kPrepRecPc, kPrepRecLo /* index in the input arrays */,
+       kPrepRecHead = 8 /* mu[n_max_stream], then w[n_max_stream] */ };
 
 // stg.n[item] of a layer diagonalised by the Rayleigh kernel: its row count + kStageDirect (the Jacobi / eigensolver
 // kernels see a count beyond their sizes and leave; the finish kernel reads the flag)
@@ -181,6 +188,8 @@ struct LdsPlan {
 SMRT_HD int active_doubles(int n_max_stream, int Lmax, int ntheta, bool with_norm0 = true) {
     return 9 * 2 * ntheta + 2 * 2 * ntheta + (2 * ntheta + 2) / 2 + 1 + (with_norm0 ? 2 * n_max_stream * Lmax : 0);
 }
+// doubles of one item record of the per-layer prep (DevStage::rec)
+SMRT_HD int prep_record_doubles(int n_max_stream) { return kPrepRecHead + 2 * n_max_stream; }
 // azimuth samples of the discrete Fourier decomposition of the phase function (emmodel/common.py:401-414)
 SMRT_HD int azimuth_samples(int m_max) {
     int e = 4, v = 1;
@@ -205,9 +214,15 @@ SMRT_HD LdsPlan make_plan(int n_max_stream, int P, int Lmax, int ntheta, int nph
     // slim = 3: the prep kernel of the LDS-resident passive pipeline -- like slim = 1, but its two symmetric matrices are
     // stored as packed lower triangles (sidx<true>, dort_dense.hpp): 34 KB instead of 67 KB at 32 streams, so that THREE
     // workgroups share a CU
-    const bool packed = (slim == 3);
-    if (packed) slim = 1;
-    const int nmat = slim ? 2 : 4;
+    // slim = 4: the layer kernel of the per-layer prep (dort_prep_layer.hpp), sized for ONE layer of a size class of rows
+    // (n_max_stream = the streams of the class): the two packed triangles, mrow / wrow / u / d, the azimuth table, the status
+    // words and the 512 doubles of Cholesky scratch -- no stream vectors, no Lmax-long tables, no tb (the item's record in
+    // the staging area has them).  14 / 25 / 40 KB for classes of 32 / 48 / 64 rows.
+    // slim = 5: the pair setup kernel of the same prep: the stream and per-layer tables of pair_setup only.
+    const bool layer = (slim == 4), setup = (slim == 5);
+    const bool packed = (slim == 3 || layer);
+    if (packed || setup) slim = 1;
+    const int nmat = setup ? 0 : slim ? 2 : 4;
     const int one = packed ? (p.LD * (p.LD + 1)) / 2 : p.NMAX * p.LD;
     p.mat_doubles = nmat * one;
     // (one 16 x 16 block inverse per block row of the triangular solve: whole blocks, also when 16 does not divide NMAX)
@@ -217,17 +232,17 @@ SMRT_HD LdsPlan make_plan(int n_max_stream, int P, int Lmax, int ntheta, int nph
     if (slim == 2) p.o_M[3] = p.NMAX * p.LD;  // the two-slot finish kernel: M0 = X, M3 = R (M1, M2 live in global memory)
     if (matrices_in_lds) o = p.mat_doubles;
     p.slim = slim;
-    p.o_rowvec = o; o += (slim == 1 ? 4 : slim == 2 ? 14 : 17) * p.NMAX;  // slim 2: no mrow / wrow / u
-    p.o_strvec = o; o += 6 * p.nmax;
-    p.o_layvec = o; o += 15 * Lmax;
-    p.o_phi = o; o += (slim == 2 ? 0 : 5 * nphi);
-    p.o_tb = o; o += p.NMAX;
-    p.o_int = o; o += 8;
+    p.o_rowvec = o; o += (setup ? 0 : slim == 1 ? 4 : slim == 2 ? 14 : 17) * p.NMAX;  // slim 2: no mrow / wrow / u
+    p.o_strvec = o; o += layer ? 0 : 6 * p.nmax;
+    p.o_layvec = o; o += layer ? 0 : 15 * Lmax;
+    p.o_phi = o; o += (slim == 2 || setup ? 0 : layer ? 3 * nphi : 5 * nphi);   // (passive assembly: cphi, s2phi, wphi)
+    p.o_tb = o; o += (layer || setup) ? 0 : p.NMAX;
+    p.o_int = o; o += layer ? 4 : 8;
     // Gauss-Jordan bookkeeping: perm [NMAX + 16] + rowblk [NMAX] + two flags (ints), then the 16 x 16 inverse of the
     // running diagonal block (fast panel): NMAX + 11 + 256 doubles
     const int gjd = p.NMAX + 12 + 256;
     const int full = ((16 * p.NMAX + 8 > 1024 + 8) ? 16 * p.NMAX + 8 : 1024 + 8) + (p.NMAX + 8 + 1) / 2;
-    p.o_gj = o; o += slim == 1 ? 520 : slim == 2 ? gjd : !matrices_in_lds ? gjd + p.NMAX / 2 + 32 : (full > gjd ? full : gjd);
+    p.o_gj = o; o += setup ? 0 : layer ? 512 : slim == 1 ? 520 : slim == 2 ? gjd : !matrices_in_lds ? gjd + p.NMAX / 2 + 32 : (full > gjd ? full : gjd);
     p.o_act = o; o += act_doubles;
     p.o_jac = -1;
     // 1: a whole matrix (Jacobi stage of the fused kernel); 2: only the 16 NMAX doubles of scratch that the blocked

@@ -226,6 +226,72 @@ SMRT_DEV int pair_setup(const DevBatch& b, const Lds& s, double frequency, int L
     return s.ints[0];
 }
 
+// One stream pair (i, j), i >= j, of the azimuth-mode-0 phase matrix of a layer: the 2 x 2 polarisation blocks of
+// S+ = P(mu_i, +mu_j) + P(mu_i, -mu_j) -> M0 and S- = P(+) - P(-) -> M1 (lower triangle by stream blocks; the matrices are
+// symmetric).  The assembly body of the per-pair drivers and of the per-layer prep kernel (dort_prep_layer.hpp): one text,
+// one order of every sum.  lo: the layer's index in the input arrays; cphi / s2phi / wphi: the azimuth table.
+template <bool PK>
+SMRT_DEV void phase_mode0_block(const DevBatch& b, long long gp, int lo, int em_l, int ms_l, double pa, double pb, double fv,
+                                double q1, double q2, double krho, const double* cphi, const double* s2phi, const double* wphi,
+                                int nphi, int i, int j, double mi, double mj, double* M0, double* M1, int LD) {
+    double pvv_p, pvh_p, phv_p, phh_p, pvv_m, pvh_m, phv_m, phh_m;
+    if (em_l == EM_HOST) {  // mode 0 of the caller's ft_even_phase(mu, +-mu'), compressed (smrt_dort.h)
+        const int NE = b.host_ne;
+        const double* hp = b.host_phase + ((gp * b.Lmax + lo) * (long long)b.host_modes) * 2 * NE * NE;   // lo: the layer's index in the input
+        const double* hm = hp + (long long)NE * NE;
+        const int r0 = 2 * i, c0 = 2 * j;
+        pvv_p = hp[r0 * NE + c0]; pvh_p = hp[r0 * NE + c0 + 1];
+        phv_p = hp[(r0 + 1) * NE + c0]; phh_p = hp[(r0 + 1) * NE + c0 + 1];
+        pvv_m = hm[r0 * NE + c0]; pvh_m = hm[r0 * NE + c0 + 1];
+        phv_m = hm[(r0 + 1) * NE + c0]; phh_m = hm[(r0 + 1) * NE + c0 + 1];
+    } else if (em_l != EM_IBA) {  // closed form, rayleigh.py:70-76; even in mu'
+        const double a2 = mi * mi, b2 = mj * mj;
+        pvv_p = pa * (0.5 * a2 * b2 + (1.0 - a2) * (1.0 - b2));
+        pvh_p = pa * 0.5 * a2; phv_p = pa * 0.5 * b2; phh_p = pa * 0.5;
+        pvv_m = pvv_p; pvh_m = pvh_p; phv_m = phv_p; phh_m = phh_p;
+    } else {
+        const double sisj = sqrt(1.0 - mi * mi) * sqrt(1.0 - mj * mj);
+        const double mm = mi * mj;
+        const double a2 = mi * mi, b2 = mj * mj;
+        pvv_p = pvh_p = phv_p = phh_p = pvv_m = pvh_m = phv_m = phh_m = 0.0;
+        for (int k = 0; k < nphi; ++k) {
+            const double c = cphi[k], s2 = s2phi[k], wk = wphi[k];
+            double ct_p = mm + sisj * c;       // cos(scattering angle), mu' = +mu_j
+            double ct_m = -mm + sisj * c;      // mu' = -mu_j
+            // (only these two bounds can be crossed, by rounding, at mu = mu': cos(ti - tj) and -cos(ti - tj);
+            // the other two are +-cos(ti + tj) with ti + tj < pi)
+            ct_p = ct_p > 1.0 ? 1.0 : ct_p;
+            ct_m = ct_m < -1.0 ? -1.0 : ct_m;
+            double Cp, Cm;
+            if (ms_l == MS_EXP) {
+                // pa wk / dp^2 and pa wk / dm^2 with ONE reciprocal (quarter rate, plus its Newton steps)
+                const double dp = 1.0 + pb * (1.0 - ct_p), dm = 1.0 + pb * (1.0 - ct_m);
+                const double dp2 = dp * dp, dm2 = dm * dm;
+                const double q = (pa * wk) * fast_rcp(dp2 * dm2);
+                Cp = dm2 * q; Cm = dp2 * q;
+            } else {
+                Cp = pa * wk * ft_corr(ms_l, pb * (1.0 - ct_p), fv, q1, q2, krho);
+                Cm = pa * wk * ft_corr(ms_l, pb * (1.0 - ct_m), fv, q1, q2, krho);
+            }
+            const double fvv_p = c * mm + sisj, fvv_m = -c * mm + sisj;
+            pvv_p += fvv_p * fvv_p * Cp; pvv_m += fvv_m * fvv_m * Cm;
+            const double s2p = s2 * Cp, s2m = s2 * Cm;          // (a2, b2 are applied once, after the loop)
+            pvh_p += s2p; pvh_m += s2m;
+            const double c2 = c * c;
+            phh_p += c2 * Cp; phh_m += c2 * Cm;
+        }
+        phv_p = b2 * pvh_p; phv_m = b2 * pvh_m;
+        pvh_p *= a2; pvh_m *= a2;
+    }
+    const int r0 = 2 * i, c0 = 2 * j;
+    M0[sidx<PK>(r0, c0, LD)] = pvv_p + pvv_m;             M1[sidx<PK>(r0, c0, LD)] = pvv_p - pvv_m;
+    if (!PK || i > j) {   // (V, H) of a diagonal stream block lies above the diagonal: its mirror (H, V) is written below
+        M0[sidx<PK>(r0, c0 + 1, LD)] = pvh_p + pvh_m;     M1[sidx<PK>(r0, c0 + 1, LD)] = pvh_p - pvh_m;
+    }
+    M0[sidx<PK>(r0 + 1, c0, LD)] = phv_p + phv_m;         M1[sidx<PK>(r0 + 1, c0, LD)] = phv_p - phv_m;
+    M0[sidx<PK>(r0 + 1, c0 + 1, LD)] = phh_p + phh_m;     M1[sidx<PK>(r0 + 1, c0 + 1, LD)] = phh_p - phh_m;
+}
+
 #ifdef SMRT_EMU_DEBUG
 #include <cstdio>
 #define SMRT_DUMP(tag, M, NN) do { block_sync(); if (t == 0) { char fn[128]; snprintf(fn, 128, "/tmp/dump_l%d_%s.bin", l, tag); FILE* f = fopen(fn, "wb"); for (int c_ = 0; c_ < (NN); ++c_) fwrite((M) + c_ * LD, 8, (NN), f); fclose(f);} block_sync(); } while (0)
@@ -487,63 +553,8 @@ SMRT_DEV void dort_pair_passive(const DevBatch& b, long long p, double* lds_base
                 while ((i + 1) * (i + 2) / 2 <= idx) ++i;
                 while (i * (i + 1) / 2 > idx) --i;
                 const int j = idx - i * (i + 1) / 2;
-                const double mi = s.mu[i], mj = s.mu[j];
-                double pvv_p, pvh_p, phv_p, phh_p, pvv_m, pvh_m, phv_m, phh_m;
-                if (em_l == EM_HOST) {  // mode 0 of the caller's ft_even_phase(mu, +-mu'), compressed (smrt_dort.h)
-                    const int NE = b.host_ne;
-                    const double* hp = b.host_phase + ((gp * b.Lmax + lo) * (long long)b.host_modes) * 2 * NE * NE;   // lo: the layer's index in the input
-                    const double* hm = hp + (long long)NE * NE;
-                    const int r0 = 2 * i, c0 = 2 * j;
-                    pvv_p = hp[r0 * NE + c0]; pvh_p = hp[r0 * NE + c0 + 1];
-                    phv_p = hp[(r0 + 1) * NE + c0]; phh_p = hp[(r0 + 1) * NE + c0 + 1];
-                    pvv_m = hm[r0 * NE + c0]; pvh_m = hm[r0 * NE + c0 + 1];
-                    phv_m = hm[(r0 + 1) * NE + c0]; phh_m = hm[(r0 + 1) * NE + c0 + 1];
-                } else if (em_l != EM_IBA) {  // closed form, rayleigh.py:70-76; even in mu'
-                    const double a2 = mi * mi, b2 = mj * mj;
-                    pvv_p = pa * (0.5 * a2 * b2 + (1.0 - a2) * (1.0 - b2));
-                    pvh_p = pa * 0.5 * a2; phv_p = pa * 0.5 * b2; phh_p = pa * 0.5;
-                    pvv_m = pvv_p; pvh_m = pvh_p; phv_m = phv_p; phh_m = phh_p;
-                } else {
-                    const double sisj = sqrt(1.0 - mi * mi) * sqrt(1.0 - mj * mj);
-                    const double mm = mi * mj;
-                    const double a2 = mi * mi, b2 = mj * mj;
-                    pvv_p = pvh_p = phv_p = phh_p = pvv_m = pvh_m = phv_m = phh_m = 0.0;
-                    for (int k = 0; k < nphi; ++k) {
-                        const double c = s.cphi[k], s2 = s.s2phi[k], wk = s.wphi[k];
-                        double ct_p = mm + sisj * c;       // cos(scattering angle), mu' = +mu_j
-                        double ct_m = -mm + sisj * c;      // mu' = -mu_j
-                        // (only these two bounds can be crossed, by rounding, at mu = mu': cos(ti - tj) and -cos(ti - tj);
-                        // the other two are +-cos(ti + tj) with ti + tj < pi)
-                        ct_p = ct_p > 1.0 ? 1.0 : ct_p;
-                        ct_m = ct_m < -1.0 ? -1.0 : ct_m;
-                        double Cp, Cm;
-                        if (ms_l == MS_EXP) {
-                            // pa wk / dp^2 and pa wk / dm^2 with ONE reciprocal (quarter rate, plus its Newton steps)
-                            const double dp = 1.0 + pb * (1.0 - ct_p), dm = 1.0 + pb * (1.0 - ct_m);
-                            const double dp2 = dp * dp, dm2 = dm * dm;
-                            const double q = (pa * wk) * fast_rcp(dp2 * dm2);
-                            Cp = dm2 * q; Cm = dp2 * q;
-                        } else {
-                            Cp = pa * wk * ft_corr(ms_l, pb * (1.0 - ct_p), fv, q1, q2, krho);
-                            Cm = pa * wk * ft_corr(ms_l, pb * (1.0 - ct_m), fv, q1, q2, krho);
-                        }
-                        const double fvv_p = c * mm + sisj, fvv_m = -c * mm + sisj;
-                        pvv_p += fvv_p * fvv_p * Cp; pvv_m += fvv_m * fvv_m * Cm;
-                        const double s2p = s2 * Cp, s2m = s2 * Cm;          // (a2, b2 are applied once, after the loop)
-                        pvh_p += s2p; pvh_m += s2m;
-                        const double c2 = c * c;
-                        phh_p += c2 * Cp; phh_m += c2 * Cm;
-                    }
-                    phv_p = b2 * pvh_p; phv_m = b2 * pvh_m;
-                    pvh_p *= a2; pvh_m *= a2;
-                }
-                const int r0 = 2 * i, c0 = 2 * j;
-                s.M0[sidx<PK>(r0, c0, LD)] = pvv_p + pvv_m;             s.M1[sidx<PK>(r0, c0, LD)] = pvv_p - pvv_m;
-                if (!PK || i > j) {   // (V, H) of a diagonal stream block lies above the diagonal: its mirror (H, V) is written below
-                    s.M0[sidx<PK>(r0, c0 + 1, LD)] = pvh_p + pvh_m;     s.M1[sidx<PK>(r0, c0 + 1, LD)] = pvh_p - pvh_m;
-                }
-                s.M0[sidx<PK>(r0 + 1, c0, LD)] = phv_p + phv_m;         s.M1[sidx<PK>(r0 + 1, c0, LD)] = phv_p - phv_m;
-                s.M0[sidx<PK>(r0 + 1, c0 + 1, LD)] = phh_p + phh_m;     s.M1[sidx<PK>(r0 + 1, c0 + 1, LD)] = phh_p - phh_m;
+                phase_mode0_block<PK>(b, gp, lo, em_l, ms_l, pa, pb, fv, q1, q2, krho, s.cphi, s.s2phi, s.wphi, nphi, i, j,
+                                      s.mu[i], s.mu[j], s.M0, s.M1, LD);
             }
         }
         block_sync();
