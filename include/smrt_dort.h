@@ -345,6 +345,14 @@ int32_t smrt_dort_set_diagonalisation(smrt_dort_ctx* ctx, int32_t mode);
  * Other batches keep their prep kernels.  Takes effect at the next upload. */
 int32_t smrt_dort_set_prep(smrt_dort_ctx* ctx, int32_t mode);
 
+/* The launches that take one size class of rows each (the per-layer prep and the symmetric eigensolver of the LDS-resident
+ * passive pipelines): mode 1, over compact lists of the items of the class, built on the device at upload from the stream
+ * counts of the layers (the grid of a launch is the number of its items; an empty class is not launched); 0, over every item
+ * of the pipeline pass, an item of another class leaving at once; -1: the default (1; the environment variable
+ * SMRT_DORT_CLASS_LISTS=0 / 1 overrides it for experiments).  The outputs are bitwise the same.  Launches in prune rounds
+ * (prune_deep_snowpack) keep the full grids.  Takes effect at the next upload. */
+int32_t smrt_dort_set_class_lists(smrt_dort_ctx* ctx, int32_t mode);
+
 /* What the uploaded batch runs on, as numbers (tests assert the designed kernel choice with these instead of wall-clock
  * ratios): info[SMRT_INFO_*], at most n entries written; returns SMRT_INFO_COUNT, -1 on error.
  *   PIPELINE      SMRT_PIPELINE_*: the kernels a launch of this batch consists of
@@ -358,10 +366,14 @@ int32_t smrt_dort_set_prep(smrt_dort_ctx* ctx, int32_t mode);
  *                 nonscattering, rayleigh-family host emmodels) of this batch skip Cholesky and the iteration: their azimuth
  *                 mode 0 is "diagonal minus rank two" and is diagonalised in closed form (passive batches on the strip finish
  *                 kernels; SMRT_DORT_RAYLEIGH=0 switches it off for experiments)
- *   PREP          SMRT_PREP_*: the prep stage of this batch (PER_LAYER only on the LDS pipelines in passive mode) */
+ *   PREP          SMRT_PREP_*: the prep stage of this batch (PER_LAYER only on the LDS pipelines in passive mode)
+ *   CLASS_LISTS   1: the launches per size class of rows of this batch run over item lists (smrt_dort_set_class_lists)
+ *   CLASS_LIST_ITEMS  items in the lists of this upload, all classes and chunks (-1: no lists)
+ *   CLASS_LIST_MISSES listed items a launch found with a staged row count of another class since the upload: always 0
+ *                 (a check of the lists against the staging area; synchronises) */
 enum { SMRT_INFO_PIPELINE = 0, SMRT_INFO_CHUNK_PAIRS, SMRT_INFO_CHUNKS, SMRT_INFO_PRUNE_ROUNDS, SMRT_INFO_STAGED_ITEMS,
        SMRT_INFO_BLOCK_THREADS, SMRT_INFO_N_MAX, SMRT_INFO_DIAGONALISATION, SMRT_INFO_RAYLEIGH_CLOSED_FORM, SMRT_INFO_PREP,
-       SMRT_INFO_COUNT };
+       SMRT_INFO_CLASS_LISTS, SMRT_INFO_CLASS_LIST_ITEMS, SMRT_INFO_CLASS_LIST_MISSES, SMRT_INFO_COUNT };
 enum { SMRT_PREP_PER_PAIR = 0, SMRT_PREP_PER_LAYER = 1 };
 enum { SMRT_DIAG_JACOBI = 0,      /* one-sided Jacobi on B = L+^T L- (singular values to high relative accuracy) */
        SMRT_DIAG_SYMMETRIC = 1 }; /* Householder tridiagonalisation + implicit QL on S = B B^T (passive, N <= 64: the default) */

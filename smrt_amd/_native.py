@@ -720,6 +720,8 @@ def load_library():
     lib.smrt_dort_set_diagonalisation.restype = C.c_int32
     lib.smrt_dort_set_prep.argtypes = [C.c_void_p, C.c_int32]
     lib.smrt_dort_set_prep.restype = C.c_int32
+    lib.smrt_dort_set_class_lists.argtypes = [C.c_void_p, C.c_int32]
+    lib.smrt_dort_set_class_lists.restype = C.c_int32
     lib.smrt_dort_gather_plan.argtypes = [C.c_int32, C.c_int32, C.c_int32, P(C.c_int64), C.c_void_p, C.c_int32,
                                           P(C.c_int64), P(C.c_int64)]
     lib.smrt_dort_gather_plan.restype = C.c_int32
@@ -939,7 +941,7 @@ EXPORTED_SYMBOLS = [
     "smrt_dort_upload", "smrt_dort_upload_pairs", "smrt_dort_run_pairs", "smrt_dort_abi", "smrt_dort_pair_cost", "smrt_dort_ft_even_phase",
     "smrt_dort_launch_info", "smrt_dort_comm_library", "smrt_dort_comm_unique_id", "smrt_dort_comm_init", "smrt_dort_comm_init_all", "smrt_dort_comm_destroy", "smrt_dort_gather",
     "smrt_dort_comm_allreduce_max", "smrt_dort_launch", "smrt_dort_sync", "smrt_dort_download", "smrt_dort_last_kernel_ms", "smrt_dort_kernel_breakdown",
-    "smrt_dort_total_kernel_ms", "smrt_dort_set_block_threads", "smrt_dort_set_pipeline", "smrt_dort_set_diagonalisation", "smrt_dort_set_prep", "smrt_dort_sum_n3", "smrt_dort_stage_cycles", "smrt_dort_device_count", "smrt_gauss_legendre_positive",
+    "smrt_dort_total_kernel_ms", "smrt_dort_set_block_threads", "smrt_dort_set_pipeline", "smrt_dort_set_diagonalisation", "smrt_dort_set_prep", "smrt_dort_set_class_lists", "smrt_dort_sum_n3", "smrt_dort_stage_cycles", "smrt_dort_device_count", "smrt_gauss_legendre_positive",
     "smrt_dort_version", "smrt_dort_finish_reg_lds_bytes", "smrt_dort_finish_strip_lds_bytes", "smrt_dort_jacobi_lds_bytes", "smrt_dort_gather_plan",
     "smrt_first_order_out_stride", "smrt_first_order_run_pairs", "smrt_first_order_upload_pairs", "smrt_first_order_launch",
     "smrt_first_order_sync", "smrt_first_order_download", "smrt_first_order_kernel_ms", "smrt_first_order_abi",
@@ -1048,6 +1050,12 @@ class DortContext:
         then one workgroup per (pair, layer) item in one launch per size class of rows) or "default"."""
         code = -1 if mode in (None, "default") else self.PREPS.index(mode)
         self._check(self._lib.smrt_dort_set_prep(self._h, code), "smrt_dort_set_prep")
+
+    def set_class_lists(self, mode="default"):
+        """The launches per size class of rows (per-layer prep, symmetric eigensolver): True, over the item lists of the classes
+        built at upload; False, over every item of a pipeline pass (an item of another class leaves at once); or "default"."""
+        code = -1 if mode in (None, "default") else int(bool(mode))
+        self._check(self._lib.smrt_dort_set_class_lists(self._h, code), "smrt_dort_set_class_lists")
 
     def run(self, batch: PackedBatch, pair_begin=0, pair_count=-1, pairs=None) -> BatchOutput:
         """One shot (H2D, kernels, D2H) for the pair range, or for the listed pair indices (row i = pairs[i])."""
@@ -1427,17 +1435,21 @@ class DortContext:
 
     def launch_info(self):
         """smrt_dort_launch_info as a dict: pipeline (name), chunk_pairs, chunks, prune_rounds, staged_items (None when
-        unknown), block_threads, n_max, diagonalisation (name), rayleigh_closed_form (bool), prep (name)."""
+        unknown), block_threads, n_max, diagonalisation (name), rayleigh_closed_form (bool), prep (name), class_lists (bool: the
+        launches per size class run over item lists), class_list_items (None without lists), class_list_misses (always 0)."""
         v = (C.c_int64 * 16)()
         n = self._lib.smrt_dort_launch_info(self._h, v, 16)
         self._check(0 if n > 0 else -1, "smrt_dort_launch_info")
         keys = ("pipeline", "chunk_pairs", "chunks", "prune_rounds", "staged_items", "block_threads", "n_max", "diagonalisation",
-                "rayleigh_closed_form", "prep")
+                "rayleigh_closed_form", "prep", "class_lists", "class_list_items", "class_list_misses")
         d = {k: int(v[i]) for i, k in enumerate(keys[:n])}
         d["pipeline"] = self.PIPELINES[d["pipeline"]]
         d["diagonalisation"] = self.DIAGONALISATIONS[d["diagonalisation"]]
         d["rayleigh_closed_form"] = bool(d.get("rayleigh_closed_form", 0))
         d["prep"] = self.PREPS[d.get("prep", 0)]
+        d["class_lists"] = bool(d.get("class_lists", 0))
+        if d.get("class_list_items", -1) < 0:
+            d["class_list_items"] = None
         if d.get("staged_items", -1) < 0:
             d["staged_items"] = None
         return d

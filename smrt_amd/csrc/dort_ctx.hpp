@@ -6,6 +6,7 @@
 #include <string>
 #include <vector>
 
+#include "dort_class_lists.hpp"
 #include "dort_layout.hpp"
 
 namespace smrt { struct PhaseRequest; struct FoBatch; }
@@ -31,7 +32,7 @@ struct smrt_dort_ctx {
     hipStream_t stream = nullptr;
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     std::string err;
-    DevBuf d_nl, d_thick, d_fv, d_temp, d_p1, d_p2, d_freq, d_theta, d_gl, d_out, d_status, d_layer, d_stream, d_n3, d_stage, d_work, d_stL, d_stB, d_std, d_sts, d_stn, d_sti, d_sub1, d_sub2, d_subT, d_atm, d_pairmap, d_kind, d_phase, d_done, d_hostlayer, d_hostcoeff, d_hoststreams, d_hostphase, d_dispatch, d_regws, d_itfslot, d_itf, d_itfcoh, d_lw, d_ste, d_strot, d_strec;
+    DevBuf d_nl, d_thick, d_fv, d_temp, d_p1, d_p2, d_freq, d_theta, d_gl, d_out, d_status, d_layer, d_stream, d_n3, d_stage, d_work, d_stL, d_stB, d_std, d_sts, d_stn, d_sti, d_sub1, d_sub2, d_subT, d_atm, d_pairmap, d_kind, d_phase, d_done, d_hostlayer, d_hostcoeff, d_hoststreams, d_hostphase, d_dispatch, d_regws, d_itfslot, d_itf, d_itfcoh, d_lw, d_ste, d_strot, d_strec, d_clrows, d_clcounts, d_cloffsets, d_cllist, d_clmiss;
     smrt::DevBatch dev{};
     bool uploaded = false;
     int out_stride = 0;
@@ -41,6 +42,13 @@ struct smrt_dort_ctx {
     size_t finish2_lds_bytes = 0;
     size_t finish_reg_lds_bytes = 0;
     size_t prep_wide_lds_bytes = 0;
+    // the item lists of the launches per size class of rows (dort_class_lists.hpp): built at upload on the passive N <= 64
+    // pipelines for the per-layer prep and the symmetric eigensolver; smrt_dort_set_class_lists / SMRT_DORT_CLASS_LISTS=0: full grids
+    int class_lists_mode = -1;  // -1 default (on), 0 off, 1 on
+    bool class_lists = false;   // this upload has lists (a round over part of the layers still launches full grids)
+    smrt::ClassListPlan class_plan;             // host: per (chunk, class) offset and count, per dispatch position the offsets
+    std::vector<int32_t> dispatch_host;         // host copies of what upload sends asynchronously
+    std::vector<int32_t> class_counts_host;
     int prep_mode = -1;         // smrt_dort_set_prep: -1 default, 0 one workgroup per pair, 1 per (pair, layer) item where built
     bool prep_layers = false;   // this batch: the per-layer prep (k_prep_layer.hip) in place of dort_prep_kernel
     bool prep_wide = false;     // 64 < N <= 128, passive: the LDS-resident prep kernel (packed triangles) with eight wavefronts
@@ -105,6 +113,10 @@ struct smrt_dort_ctx {
 #define SMRT_JACOBI_NT 256   // threads per workgroup of the Jacobi kernel
 #endif
 
+// The lists of one chunk for the launches per size class of rows: device pointer to and length of the chunk's segment of
+// every class (null pointer to the struct: the launches cover every item of the round)
+struct ClassSegments { const int* list[smrt::kRowClasses]; long long count[smrt::kRowClasses]; };
+
 // Kernel launchers, one translation unit each (asynchronous on ctx->stream; the returned error is the launch error).
 // `c` is the DevBatch of one chunk (pair_begin / pair_count / output pointers already offset).
 namespace smrt_launch {
@@ -114,8 +126,8 @@ hipError_t prep_wide(smrt_dort_ctx* ctx, const smrt::DevBatch& c);   // the same
 hipError_t finish(smrt_dort_ctx* ctx, const smrt::DevBatch& c, int nt, bool two_slot);
 void occupancy_report(smrt_dort_ctx* ctx, int nt);
 // k_prep_layer.hip: the per-layer prep of the same pipelines -- pair setup, then one layer kernel launch per size class of rows
-// over the `items` (pair, layer) items of the round
-hipError_t prep_layers(smrt_dort_ctx* ctx, const smrt::DevBatch& c, long long items);
+// over the `items` (pair, layer) items of the round, or over the chunk's list of the class (seg)
+hipError_t prep_layers(smrt_dort_ctx* ctx, const smrt::DevBatch& c, long long items, const ClassSegments* seg);
 // k_finish_reg.hip: the register-resident finish kernel of the same pipeline, one wavefront per pair
 hipError_t finish_reg(smrt_dort_ctx* ctx, const smrt::DevBatch& c);
 // k_finish_strip.hip: the strip finish kernel of the 64 < N <= 128 pipeline (passive), one workgroup of eight wavefronts per pair
@@ -124,7 +136,17 @@ hipError_t finish_strip4(smrt_dort_ctx* ctx, const smrt::DevBatch& c);   // N <=
 // k_jacobi.hip: one workgroup per staging item (pair, [azimuth mode,] layer)
 hipError_t jacobi(smrt_dort_ctx* ctx, const smrt::DevBatch& c, long long items);
 // k_eig.hip: the symmetric eigensolver on the same items (N <= 64): tridiag, chase, vectors
-hipError_t eig(smrt_dort_ctx* ctx, const smrt::DevBatch& c, long long items);
+hipError_t eig(smrt_dort_ctx* ctx, const smrt::DevBatch& c, long long items, const ClassSegments* seg);
+// the launch of class (LO, HI] of those two: through the chunk's list of the class its grid is the length of the list (false: the
+// list is empty, nothing to launch); without lists the grid stays `items`
+template <int LO, int HI>
+inline bool class_launch(smrt::DevBatch& cl, long long& items, const ClassSegments* seg) {
+    if (!seg) return true;
+    constexpr int k = smrt::row_class_index<LO, HI>();
+    if (seg->count[k] == 0) return false;
+    cl.class_list = seg->list[k]; items = seg->count[k];
+    return true;
+}
 // k_rayleigh.hip: the layers with a Rayleigh phase matrix in closed form (passive; the other kernels skip them)
 hipError_t rayleigh(smrt_dort_ctx* ctx, const smrt::DevBatch& c, long long items);
 // k_split_active.hip
@@ -144,8 +166,10 @@ hipError_t fused_gmem(smrt_dort_ctx* ctx, const smrt::DevBatch& d, int ch, bool 
 hipError_t ft_even_phase(smrt_dort_ctx* ctx, const smrt::PhaseRequest& q);
 // k_cost.hip: which pairs have reached their prune_deep_snowpack cut within the layers processed so far
 hipError_t prune_mark(smrt_dort_ctx* ctx, const smrt::DevBatch& c, int* done_dev);
-// k_cost.hip: sum of N_l^3 per pair from the stream counts alone
-hipError_t pair_cost(smrt_dort_ctx* ctx, const smrt::DevBatch& d, double* cost_dev);
+// k_cost.hip: sum of N_l^3 per pair from the stream counts alone; with class_rows_dev [pair_count][Lmax] and class_counts_dev
+// [pair_count][kRowClasses] (or null) also the count step of the class lists, and their fill step
+hipError_t pair_cost(smrt_dort_ctx* ctx, const smrt::DevBatch& d, double* cost_dev, int* class_rows_dev = nullptr, int* class_counts_dev = nullptr);
+hipError_t class_fill(smrt_dort_ctx* ctx, const smrt::DevBatch& d, long long chunk_pairs, const int* rows_dev, const long long* pair_offset_dev, int* list_dev);
 // one per solver beside DORT, each in the solver's file: frees the solver's state on the context (smrt_dort_destroy)
 void first_order_release(smrt_dort_ctx* ctx);
 void successive_order_release(smrt_dort_ctx* ctx);

@@ -27,6 +27,7 @@
 
 // The device code in reading order:
 #include "dort_layout.hpp"         // descriptors, LDS plan
+#include "dort_class_lists.hpp"    // item lists of the launches per size class of rows
 #include "dort_physics.hpp"        // layer electromagnetics, Fresnel, Planck
 #include "dort_dense.hpp"          // Cholesky, triangular kernels, GEMM passes, in-kernel Jacobi
 #include "dort_gauss_jordan.hpp"   // blocked Gauss-Jordan

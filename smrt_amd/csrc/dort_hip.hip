@@ -65,8 +65,8 @@ static hipError_t launch_pipeline(smrt_dort_ctx* ctx, const DevBatch& d) {
     // (under process_coherent_layers the layer indices of a pair are its own: one round, and the staging counts of the
     // removed layers must read "nothing staged")
     const int rounds = (d.prune_tau > 0.0 && !d.coherent && getenv("SMRT_DORT_NO_PRUNE_ROUNDS") == nullptr) ? std::min(4, d.Lmax) : 1;
-    auto prep = [&](const DevBatch& c, unsigned grid) {
-        if (ctx->prep_layers) return smrt_launch::prep_layers(ctx, c, c.pair_count * (c.layer_hi - c.layer_lo));
+    auto prep = [&](const DevBatch& c, unsigned grid, const ClassSegments* seg) {
+        if (ctx->prep_layers) return smrt_launch::prep_layers(ctx, c, c.pair_count * (c.layer_hi - c.layer_lo), seg);
         if (ctx->big) return smrt_launch::prep_gmem_big(ctx, c, grid, ctx->active, ctx->nmax_rows <= 256 ? 4 : 6);
         if (ctx->prep_wide) return smrt_launch::prep_wide(ctx, c);
         if (ctx->gmem_split) return smrt_launch::prep_gmem(ctx, c, grid, ctx->active);
@@ -138,12 +138,20 @@ static hipError_t launch_pipeline(smrt_dort_ctx* ctx, const DevBatch& d) {
             if ((e = hipMemsetAsync(done_lane, 0, sizeof(int) * (size_t)cn, ctx->stream)) != hipSuccess) return e;
             c.pair_done = (const int*)done_lane;
         }
+        // the chunk's item lists for the launches per size class of rows; a round over part of the layers launches full grids
+        ClassSegments segs{};
+        const bool listed = ctx->class_lists && rounds == 1 && chunk_index < ctx->class_plan.chunks;
+        for (int k = 0; listed && k < kRowClasses; ++k) {
+            segs.list[k] = (const int*)ctx->d_cllist.p + ctx->class_plan.seg_offset[(size_t)chunk_index * kRowClasses + k];
+            segs.count[k] = ctx->class_plan.seg_count[(size_t)chunk_index * kRowClasses + k];
+        }
+        const ClassSegments* seg = listed ? &segs : nullptr;
         for (int r = 0; r < rounds; ++r) {
             c.layer_lo = (int)((long long)d.Lmax * r / rounds);
             c.layer_hi = (int)((long long)d.Lmax * (r + 1) / rounds);
-            if ((e = timed(0, [&]() { return prep(c, grid); })) != hipSuccess) return e;
+            if ((e = timed(0, [&]() { return prep(c, grid, seg); })) != hipSuccess) return e;
             const long long jitems = cn * modes * (c.layer_hi - c.layer_lo);
-            if ((e = timed(1, [&]() { hipError_t e1 = ctx->big ? smrt_launch::jacobi_big(ctx, c, jitems) : ctx->eig ? smrt_launch::eig(ctx, c, jitems) : smrt_launch::jacobi(ctx, c, jitems);
+            if ((e = timed(1, [&]() { hipError_t e1 = ctx->big ? smrt_launch::jacobi_big(ctx, c, jitems) : ctx->eig ? smrt_launch::eig(ctx, c, jitems, seg) : smrt_launch::jacobi(ctx, c, jitems);
                                            if (e1 == hipSuccess && c.rayleigh_direct) e1 = smrt_launch::rayleigh(ctx, c, jitems);   // (its items leave the other kernels at once)
                                            return e1; })) != hipSuccess) return e;
             if (r + 1 < rounds && (e = smrt_launch::prune_mark(ctx, c, done_lane)) != hipSuccess) return e;
@@ -206,7 +214,7 @@ void smrt_dort_destroy(smrt_dort_ctx* ctx) {
     DevBuf* bufs[] = {&ctx->d_nl, &ctx->d_thick, &ctx->d_fv, &ctx->d_temp, &ctx->d_p1, &ctx->d_p2, &ctx->d_freq,
                       &ctx->d_theta, &ctx->d_gl, &ctx->d_out, &ctx->d_status, &ctx->d_layer, &ctx->d_stream, &ctx->d_n3, &ctx->d_stage, &ctx->d_work,
                       &ctx->d_stL, &ctx->d_stB, &ctx->d_std, &ctx->d_sts, &ctx->d_stn, &ctx->d_sti, &ctx->d_ste, &ctx->d_strot, &ctx->d_strec, &ctx->d_regws, &ctx->d_itfslot, &ctx->d_itf, &ctx->d_itfcoh,
-                      &ctx->d_sub1, &ctx->d_sub2, &ctx->d_subT, &ctx->d_atm, &ctx->d_pairmap, &ctx->d_kind, &ctx->d_hostlayer, &ctx->d_hoststreams, &ctx->d_hostphase, &ctx->d_dispatch, &ctx->d_phase, &ctx->d_done, &ctx->d_lw, &ctx->d_gather_out, &ctx->d_gather_status,
+                      &ctx->d_sub1, &ctx->d_sub2, &ctx->d_subT, &ctx->d_atm, &ctx->d_pairmap, &ctx->d_kind, &ctx->d_hostlayer, &ctx->d_hoststreams, &ctx->d_hostphase, &ctx->d_dispatch, &ctx->d_phase, &ctx->d_done, &ctx->d_lw, &ctx->d_clrows, &ctx->d_clcounts, &ctx->d_cloffsets, &ctx->d_cllist, &ctx->d_clmiss, &ctx->d_gather_out, &ctx->d_gather_status,
                       &ctx->d_scalar};
     for (DevBuf* b : bufs) b->release();
     smrt_launch::first_order_release(ctx);
@@ -253,6 +261,14 @@ int32_t smrt_dort_set_prep(smrt_dort_ctx* ctx, int32_t mode) {
     if (mode < -1 || mode > SMRT_PREP_PER_LAYER) { ctx->err = "unknown prep mode"; return -1; }
     ctx->prep_mode = mode;
     ctx->uploaded = false;  // the staging area is sized at upload time
+    return 0;
+}
+
+int32_t smrt_dort_set_class_lists(smrt_dort_ctx* ctx, int32_t mode) {
+    if (!ctx) return -1;
+    if (mode < -1 || mode > 1) { ctx->err = "unknown class list mode"; return -1; }
+    ctx->class_lists_mode = mode;
+    ctx->uploaded = false;  // the lists are built at upload time
     return 0;
 }
 
@@ -340,6 +356,12 @@ static int32_t upload_impl(smrt_dort_ctx* ctx, const smrt_batch* b, int64_t pair
         ctx->prep_layers = !ctx->gmem_path && ctx->split && !ctx->active && plan.NMAX <= 64 && want == SMRT_PREP_PER_LAYER;
     }
     const size_t rec_doubles = ctx->prep_layers ? (size_t)prep_record_doubles(b->n_max_stream) : 0;
+    // the item lists of the launches per size class of rows (dort_class_lists.hpp): wanted unless switched off; whether this
+    // batch has such launches is known below (ctx->eig)
+    bool want_lists = ctx->class_lists_mode != 0;
+    if (const char* e = getenv("SMRT_DORT_CLASS_LISTS")) want_lists = atoi(e) != 0;
+    ctx->class_lists = false;
+    ctx->class_plan.clear();
     // N > 128: the pipeline with the blocked Jacobi kernel (matrix in the staging area, column blocks through LDS)
     int big_min = 128;   // SMRT_DORT_BIG_MIN_N: experiments with the big pipeline on smaller matrices
     if (const char* e = getenv("SMRT_DORT_BIG_MIN_N")) big_min = std::max(64, atoi(e));
@@ -360,7 +382,8 @@ static int32_t upload_impl(smrt_dort_ctx* ctx, const smrt_batch* b, int64_t pair
         const size_t nmodes = ctx->active ? (size_t)b->m_max + 1 : 1;   // staging items per layer
         const size_t mat = (size_t)plan.NMAX * plan.LD;
         const int linv_stride = (plan.NMAX > 64) ? 2048 : 1024;   // inverses of the diagonal blocks of L+: four or eight of 256 doubles
-        const size_t per_pair = nmodes * b->n_layers_max * ((2 * mat + 2 * plan.NMAX + linv_stride + rec_doubles) * sizeof(double) + sizeof(int));
+        const size_t per_pair = nmodes * b->n_layers_max * ((2 * mat + 2 * plan.NMAX + linv_stride + rec_doubles) * sizeof(double) + sizeof(int) +
+                                                                  (want_lists && !ctx->active && plan.NMAX <= 64 ? 2 * sizeof(int) : 0));   // (rows and list entry of an item)
         // staging budget: 12 GB, or -- for the large matrices of the big pipeline, where 12 GB hold too few pairs to fill
         // the chip -- up to 60 % of the free device memory
         double budget = 12.0e9;
@@ -387,6 +410,8 @@ static int32_t upload_impl(smrt_dort_ctx* ctx, const smrt_batch* b, int64_t pair
             if (const char* e = getenv("SMRT_DORT_EIG")) want = atoi(e) ? SMRT_DIAG_SYMMETRIC : SMRT_DIAG_JACOBI;
             ctx->eig = !ctx->gmem_path && !ctx->active && plan.NMAX <= 64 && want == SMRT_DIAG_SYMMETRIC;
         }
+        // (item indices in the lists are ints, local to a chunk)
+        ctx->class_lists = want_lists && (ctx->prep_layers || ctx->eig) && chunk * (long long)b->n_layers_max < 0x7fffffffLL;
         ctx->lanes = 1;
         if (!ctx->gmem_path) {   // (the global-workspace pipelines share one per-workgroup workspace: one pass at a time)
             // With the eigensolver, three concurrent passes by default: its chase kernel is a latency chain of two wavefronts
@@ -623,6 +648,7 @@ static int32_t upload_impl(smrt_dort_ctx* ctx, const smrt_batch* b, int64_t pair
     d.atm_trans = has_atm ? (const double*)ctx->d_atm.p + 2 * b->n_frequencies : nullptr;
     d.prune_tau = (b->prune_optical_depth > 0.0) ? b->prune_optical_depth : 0.0;
     d.layer_lo = 0; d.layer_hi = b->n_layers_max; d.pair_done = nullptr;
+    d.class_list = nullptr; d.class_miss = nullptr;
     if (d.prune_tau > 0.0) HIPCHK(ctx->d_done.reserve(sizeof(int) * (size_t)std::max<long long>(ctx->chunk_pairs, 1) * ctx->lanes));
     // Jacobi thresholds on the squared cosine between two columns: below skip2 a pair is not rotated, a sweep without
     // a rotation above exit2 is the last one (dort_jacobi_kernel.hpp).  SMRT_DORT_JACOBI_SKIP2 / _EXIT2 override them
@@ -652,22 +678,48 @@ static int32_t upload_impl(smrt_dort_ctx* ctx, const smrt_batch* b, int64_t pair
     // stream counts: a cheap kernel).  Neighbouring workgroups -- the ones that share a CU -- then work on matrices of the
     // same size: 59.9 instead of 61.4 ms on the headline batch, whichever way the sort goes (tools/lpt_order_probe.py).
     // The outputs stay in the caller's order (only the workgroup -> pair map changes).  SMRT_DORT_NO_COST_ORDER=1: off.
+    // The same kernel counts, per pair, its items in every size class of rows; the counts come back with the costs, and once
+    // the dispatch order is known the lists are laid out (host) and filled (device, on the stream: before any launch).
     d.dispatch = nullptr;
-    if (pair_count > 1 && getenv("SMRT_DORT_NO_COST_ORDER") == nullptr) {
-        HIPCHK(smrt_launch::pair_cost(ctx, d, d.n3_out));
+    const bool cost_order = pair_count > 1 && getenv("SMRT_DORT_NO_COST_ORDER") == nullptr;
+    if (cost_order || ctx->class_lists) {
+        const long long Lmax = b->n_layers_max;
+        int *rows_dev = nullptr, *counts_dev = nullptr;
+        if (ctx->class_lists) {
+            HIPCHK(ctx->d_clrows.reserve(sizeof(int) * (size_t)(pair_count * Lmax)));
+            HIPCHK(ctx->d_clcounts.reserve(sizeof(int) * (size_t)pair_count * kRowClasses));
+            HIPCHK(ctx->d_clmiss.reserve(sizeof(unsigned long long)));
+            HIPCHK(hipMemsetAsync(ctx->d_clmiss.p, 0, sizeof(unsigned long long), ctx->stream));
+            rows_dev = (int*)ctx->d_clrows.p; counts_dev = (int*)ctx->d_clcounts.p;
+            d.class_miss = (unsigned long long*)ctx->d_clmiss.p;
+        }
+        HIPCHK(smrt_launch::pair_cost(ctx, d, d.n3_out, rows_dev, counts_dev));
         std::vector<double> cost((size_t)pair_count);
         HIPCHK(hipMemcpyAsync(cost.data(), d.n3_out, sizeof(double) * cost.size(), hipMemcpyDeviceToHost, ctx->stream));
-        HIPCHK(hipStreamSynchronize(ctx->stream));
-        std::vector<int32_t> order((size_t)pair_count);
-        const long long chunk = ctx->chunk_pairs > 0 ? ctx->chunk_pairs : pair_count;
-        for (long long c0 = 0; c0 < pair_count; c0 += chunk) {
-            const long long cn = std::min<long long>(chunk, pair_count - c0);
-            for (long long i = 0; i < cn; ++i) order[(size_t)(c0 + i)] = (int32_t)i;    // chunk-local pair slots
-            std::stable_sort(order.begin() + c0, order.begin() + c0 + cn,
-                             [&](int32_t a, int32_t b2) { return cost[(size_t)(c0 + a)] > cost[(size_t)(c0 + b2)]; });
+        if (ctx->class_lists) {
+            ctx->class_counts_host.resize((size_t)pair_count * kRowClasses);
+            HIPCHK(hipMemcpyAsync(ctx->class_counts_host.data(), counts_dev, sizeof(int32_t) * ctx->class_counts_host.size(), hipMemcpyDeviceToHost, ctx->stream));
         }
-        if (upload_array(ctx, ctx->d_dispatch, order.data(), sizeof(int32_t) * order.size())) return -1;
-        d.dispatch = (const int*)ctx->d_dispatch.p;
+        HIPCHK(hipStreamSynchronize(ctx->stream));
+        const long long chunk = ctx->chunk_pairs > 0 ? ctx->chunk_pairs : pair_count;
+        if (cost_order) {
+            std::vector<int32_t>& order = ctx->dispatch_host;
+            order.resize((size_t)pair_count);
+            for (long long c0 = 0; c0 < pair_count; c0 += chunk) {
+                const long long cn = std::min<long long>(chunk, pair_count - c0);
+                for (long long i = 0; i < cn; ++i) order[(size_t)(c0 + i)] = (int32_t)i;    // chunk-local pair slots
+                std::stable_sort(order.begin() + c0, order.begin() + c0 + cn,
+                                 [&](int32_t a, int32_t b2) { return cost[(size_t)(c0 + a)] > cost[(size_t)(c0 + b2)]; });
+            }
+            if (upload_array(ctx, ctx->d_dispatch, order.data(), sizeof(int32_t) * order.size())) return -1;
+            d.dispatch = (const int*)ctx->d_dispatch.p;
+        }
+        if (ctx->class_lists) {
+            ctx->class_plan = make_class_list_plan(ctx->class_counts_host.data(), cost_order ? ctx->dispatch_host.data() : nullptr, pair_count, chunk);
+            if (upload_array(ctx, ctx->d_cloffsets, ctx->class_plan.pair_offset.data(), sizeof(long long) * ctx->class_plan.pair_offset.size())) return -1;
+            HIPCHK(ctx->d_cllist.reserve(sizeof(int) * (size_t)std::max<long long>(ctx->class_plan.total, 1)));
+            HIPCHK(smrt_launch::class_fill(ctx, d, chunk, rows_dev, (const long long*)ctx->d_cloffsets.p, (int*)ctx->d_cllist.p));
+        }
     }
     return 0;
 }
@@ -829,6 +881,17 @@ int32_t smrt_dort_launch_info(smrt_dort_ctx* ctx, int64_t* info, int32_t n) {
     v[SMRT_INFO_DIAGONALISATION] = (three && ctx->eig) ? SMRT_DIAG_SYMMETRIC : SMRT_DIAG_JACOBI;
     v[SMRT_INFO_RAYLEIGH_CLOSED_FORM] = (three && d.rayleigh_direct) ? 1 : 0;
     v[SMRT_INFO_PREP] = (lds_pipeline && ctx->prep_layers) ? SMRT_PREP_PER_LAYER : SMRT_PREP_PER_PAIR;
+    // (lists are built per upload; a launch in prune rounds still runs full grids)
+    v[SMRT_INFO_CLASS_LISTS] = (lds_pipeline && ctx->class_lists && rounds == 1) ? 1 : 0;
+    v[SMRT_INFO_CLASS_LIST_ITEMS] = (lds_pipeline && ctx->class_lists) ? ctx->class_plan.total : -1;
+    v[SMRT_INFO_CLASS_LIST_MISSES] = 0;
+    if (lds_pipeline && ctx->class_lists) {   // synchronises
+        unsigned long long misses = 0;
+        HIPCHK(hipSetDevice(ctx->device));
+        HIPCHK(hipStreamSynchronize(ctx->stream));
+        HIPCHK(hipMemcpy(&misses, ctx->d_clmiss.p, sizeof(misses), hipMemcpyDeviceToHost));
+        v[SMRT_INFO_CLASS_LIST_MISSES] = (int64_t)misses;
+    }
     for (int k = 0; k < n && k < SMRT_INFO_COUNT; ++k) info[k] = v[k];
     return SMRT_INFO_COUNT;
 }

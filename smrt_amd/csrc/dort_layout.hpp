@@ -76,6 +76,12 @@ struct DevBatch {
     // stages their scalars, dort_rayleigh_kernel.hpp diagonalises them in closed form and the strip finish kernels take
     // A+ = D V as it is (host: only where a strip finish kernel consumes the staging area)
     int rayleigh_direct;
+    // The launches that take one size class of rows each (per-layer prep, symmetric eigensolver): the compact list of the
+    // chunk's items of THIS launch's class (dort_class_lists.hpp: built at upload, dispatch order of the pairs, layers
+    // ascending; chunk-local item indices), or null: the launch covers every item of the round and an item of another class
+    // leaves at once.  The list only says who is dispatched: the kernels' own filters stay.
+    const int* class_list;
+    unsigned long long* class_miss;   // counts the listed items whose staged row count is of another class (must stay 0)
 };
 
 // Staging area of the three-kernel pipeline (prep -> jacobi -> finish): per (pair, layer) the Cholesky factor L+,
@@ -128,6 +134,23 @@ SMRT_DEV long long jacobi_item_of_block(const DevBatch& b, long long blk) {
         row = (long long)b.dispatch[row / nmodes] * nmodes + row % nmodes;
     }
     return row * b.Lmax + b.layer_lo + (blk % span);
+}
+
+// ... of a size-class launch: through the class list where the launch has one (its grid is the length of the list)
+SMRT_DEV long long class_item_of_block(const DevBatch& b, long long blk) {
+    return b.class_list ? (long long)b.class_list[blk] : jacobi_item_of_block(b, blk);
+}
+// A workgroup of a size-class launch leaves because its item has `rows` rows outside the class: under a list that is a
+// disagreement between the list and the staging area unless nothing is staged (rows == 0: a filter of the kernel said no).
+// Cold path, one vector atomic by one lane.
+SMRT_DEV void class_list_left(const DevBatch& b, int rows) {
+    if (b.class_list && rows > 0 && tid() == 0) {
+#if defined(SMRT_HOST_EMU)
+        ++*b.class_miss;
+#else
+        atomicAdd(b.class_miss, 1ULL);
+#endif
+    }
 }
 
 constexpr double kCSpeed = 299792458.0;

@@ -7,6 +7,7 @@
 #include <string.h>
 #include "dort_gauss_jordan.hpp"
 #include "dort_interface_dense.hpp"
+#include "dort_class_lists.hpp"
 
 namespace smrt {
 
@@ -843,6 +844,36 @@ SMRT_DEV void dort_pair_passive(const DevBatch& b, long long p, double* lds_base
         for (int k = 0; k < 3; ++k) b.stage_out[p * 16 + 13 + k] = sub_acc_store[k];
     }
 #endif
+}
+
+// Work estimate of pair slot p for cost-weighted sharding and the dispatch order: sum over the layers (and azimuth
+// modes) of N_l^3 with the actual stream counts, from the first stage of the solve only.  With class_rows the same stream
+// counts also give the count step of the class lists (dort_class_lists.hpp).  One wavefront; the body of dort_cost_kernel.
+template <int NT>
+SMRT_DEV void dort_cost_pair(const DevBatch& b, long long p, double* lds_base, double* cost, int* class_rows, int* class_counts) {
+    const int P = b.mode == 1 ? 3 : 2;
+    const LdsPlan plan = make_plan(b.n_max_stream, P, b.Lmax, b.n_theta, 1, 0, 0, 1);
+    Lds s = carve(lds_base, lds_base, plan);
+    const int t = tid();
+    if (t < 8) s.ints[t] = 0;
+    block_sync();
+    const long long gp = global_pair(b, p);
+    const int fi = (int)(gp / b.S), si = (int)(gp % b.S);
+    int L = b.n_layers[si];
+    const long long o = (long long)si * b.Lmax;
+    const int st = pair_setup<NT>(b, s, b.frequency[fi], L, b.thickness + o, b.frac_volume + o, b.temperature + o, b.p1 + o, b.p2 + o,
+                                  b.layer_kind ? b.layer_kind + o : nullptr, gp);
+    if (st == ST_OK) L = s.ints[6];
+    if (t == 0) {
+        double c = 0.0;
+        if (st == ST_OK)
+            for (int l = 0; l < L; ++l) {
+                const double n2 = 2.0 * s.nl[l], n3 = 3.0 * s.nl[l];
+                c += n2 * n2 * n2 + (b.mode == 1 ? b.m_max * n3 * n3 * n3 : 0.0);
+            }
+        cost[p] = c;
+        if (class_rows) class_count_pair(b, s, st, p, class_rows, class_counts);
+    }
 }
 
 }  // namespace smrt

@@ -13,6 +13,7 @@
 // optical depth from the top -- still runs after the diagonalisation of a round, as with the per-pair kernel.
 // Part of the DORT device code (see dort_device.hpp for the overview and the reference map).
 #pragma once
+#include "dort_class_lists.hpp"
 #include "dort_passive.hpp"
 
 namespace smrt {
@@ -61,7 +62,7 @@ SMRT_DEV void dort_prep_setup_pair(const DevBatch& b, long long p, double* lds_b
         if (t == 0) {
             rec[kPrepRecN] = (double)n; rec[kPrepRecKe] = s.ks[l] + s.ka[l]; rec[kPrepRecKs] = s.ks[l];
             rec[kPrepRecPa] = s.pa[l]; rec[kPrepRecPb] = s.pb[l]; rec[kPrepRecPc] = s.pc[l]; rec[kPrepRecLo] = s.lo[l];
-            stg.n[item] = 2 * n;   // the layer kernel's size class; it replaces it by -status where the layer fails
+            stg.n[item] = setup_item_rows(s, l);   // 2 n, the layer kernel's size class (and what the class lists of the upload were built from); it replaces it by -status where the layer fails
         }
     }
     if (t == 0) b.status[p] = ST_OK;

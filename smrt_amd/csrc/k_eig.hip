@@ -9,7 +9,8 @@ using namespace smrt;
 
 // One wavefront per item; a launch holds the instantiations of the padded row counts of ITS size class (LO, HI] only, so
 // that the small items run with the registers (and, in tridiag, the LDS) of their own size; an item of another class
-// leaves at once (like dort_jacobi_kernel).
+// leaves at once (like dort_jacobi_kernel).  A launch takes the chunk's list of its class (dort_class_lists.hpp) or, without
+// one, every item of the round.
 #define SMRT_EIG_ROWS(NP_, CALL) \
     if constexpr (LO < (NP_) && (NP_) - 8 < HI) if (rows <= (NP_)) { CALL; return; }
 #define SMRT_EIG_ROWS16(NP_, CALL) \
@@ -17,18 +18,18 @@ using namespace smrt;
 
 template <int LO, int HI>
 __global__ __launch_bounds__(64) void dort_eig_gram_kernel(DevBatch b, DevStage st) {
-    const long long item = uniform(jacobi_item_of_block(b, (long long)blockIdx.x));
+    const long long item = uniform(class_item_of_block(b, (long long)blockIdx.x));
     const int rows = uniform(eig_item_rows(b, st, item));
-    if (rows <= LO || rows > HI) return;
+    if (rows <= LO || rows > HI) { class_list_left(b, rows); return; }
     SMRT_EIG_ROWS16(16, (eig_gram_item<16>(st, item))) SMRT_EIG_ROWS16(32, (eig_gram_item<32>(st, item)))
     SMRT_EIG_ROWS16(48, (eig_gram_item<48>(st, item))) SMRT_EIG_ROWS16(64, (eig_gram_item<64>(st, item)))
 }
 
 template <int LO, int HI>
 __global__ __launch_bounds__(64) void dort_eig_tridiag_kernel(DevBatch b, DevStage st) {
-    const long long item = uniform(jacobi_item_of_block(b, (long long)blockIdx.x));
+    const long long item = uniform(class_item_of_block(b, (long long)blockIdx.x));
     const int rows = uniform(eig_item_rows(b, st, item));
-    if (rows <= LO || rows > HI) return;
+    if (rows <= LO || rows > HI) { class_list_left(b, rows); return; }
     SMRT_EIG_ROWS(8, (eig_tridiag_item<8>(st, item))) SMRT_EIG_ROWS(16, (eig_tridiag_item<16>(st, item)))
     SMRT_EIG_ROWS(24, (eig_tridiag_item<24>(st, item))) SMRT_EIG_ROWS(32, (eig_tridiag_item<32>(st, item)))
     SMRT_EIG_ROWS(40, (eig_tridiag_item<40>(st, item))) SMRT_EIG_ROWS(48, (eig_tridiag_item<48>(st, item)))
@@ -38,9 +39,9 @@ __global__ __launch_bounds__(64) void dort_eig_tridiag_kernel(DevBatch b, DevSta
 template <int LO, int HI>
 __global__ __launch_bounds__(64) void dort_eig_vectors_kernel(DevBatch b, DevStage st) {
     __shared__ __attribute__((aligned(16))) double ring[2 * kEigRingSlots];
-    const long long item = uniform(jacobi_item_of_block(b, (long long)blockIdx.x));
+    const long long item = uniform(class_item_of_block(b, (long long)blockIdx.x));
     const int rows = uniform(eig_item_rows(b, st, item));
-    if (rows <= LO || rows > HI) return;
+    if (rows <= LO || rows > HI) { class_list_left(b, rows); return; }
     SMRT_EIG_ROWS(8, (eig_vectors_item<8>(st, item, ring))) SMRT_EIG_ROWS(16, (eig_vectors_item<16>(st, item, ring)))
     SMRT_EIG_ROWS(24, (eig_vectors_item<24>(st, item, ring))) SMRT_EIG_ROWS(32, (eig_vectors_item<32>(st, item, ring)))
     SMRT_EIG_ROWS(40, (eig_vectors_item<40>(st, item, ring))) SMRT_EIG_ROWS(48, (eig_vectors_item<48>(st, item, ring)))
@@ -66,33 +67,39 @@ __global__ __launch_bounds__(kEigChaseLanes) void dort_eig_chase_kernel(DevBatch
 
 namespace smrt_launch {
 template <int LO, int HI>
-static hipError_t go_gram(smrt_dort_ctx* ctx, const DevBatch& c, long long items) {
-    hipLaunchKernelGGL((dort_eig_gram_kernel<LO, HI>), dim3((unsigned)items), dim3(64), 0, ctx->stream, c, ctx->stage);
+static hipError_t go_gram(smrt_dort_ctx* ctx, const DevBatch& c, long long items, const ClassSegments* seg) {
+    DevBatch cl = c;
+    if (!class_launch<LO, HI>(cl, items, seg)) return hipSuccess;
+    hipLaunchKernelGGL((dort_eig_gram_kernel<LO, HI>), dim3((unsigned)items), dim3(64), 0, ctx->stream, cl, ctx->stage);
     return hipGetLastError();
 }
 template <int LO, int HI>
-static hipError_t go_tridiag(smrt_dort_ctx* ctx, const DevBatch& c, long long items) {
-    hipLaunchKernelGGL((dort_eig_tridiag_kernel<LO, HI>), dim3((unsigned)items), dim3(64), 0, ctx->stream, c, ctx->stage);
+static hipError_t go_tridiag(smrt_dort_ctx* ctx, const DevBatch& c, long long items, const ClassSegments* seg) {
+    DevBatch cl = c;
+    if (!class_launch<LO, HI>(cl, items, seg)) return hipSuccess;
+    hipLaunchKernelGGL((dort_eig_tridiag_kernel<LO, HI>), dim3((unsigned)items), dim3(64), 0, ctx->stream, cl, ctx->stage);
     return hipGetLastError();
 }
 template <int LO, int HI>
-static hipError_t go_vectors(smrt_dort_ctx* ctx, const DevBatch& c, long long items) {
-    hipLaunchKernelGGL((dort_eig_vectors_kernel<LO, HI>), dim3((unsigned)items), dim3(64), 0, ctx->stream, c, ctx->stage);
+static hipError_t go_vectors(smrt_dort_ctx* ctx, const DevBatch& c, long long items, const ClassSegments* seg) {
+    DevBatch cl = c;
+    if (!class_launch<LO, HI>(cl, items, seg)) return hipSuccess;
+    hipLaunchKernelGGL((dort_eig_vectors_kernel<LO, HI>), dim3((unsigned)items), dim3(64), 0, ctx->stream, cl, ctx->stage);
     return hipGetLastError();
 }
 
 // Size classes by row count: (0, 32], (32, 48], (48, 64] -- the register rows of tridiag / vectors are 64 / 96 / 128 registers
 // (3 / 3 / 2 wavefronts per SIMD).  Measured and dropped: a class (48, 56] of its own held to three wavefronts per SIMD by
 // __launch_bounds__ (52 / 12 B of scratch): tridiag 2.61 against 2.02 ms for the two classes, vectors 3.34 against 3.47.
-hipError_t eig(smrt_dort_ctx* ctx, const DevBatch& c, long long items) {
+hipError_t eig(smrt_dort_ctx* ctx, const DevBatch& c, long long items, const ClassSegments* seg) {
     const int nmax = ctx->nmax_rows;
     hipError_t e;
-    if ((e = go_gram<0, 32>(ctx, c, items)) != hipSuccess) return e;
-    if (nmax > 32 && (e = go_gram<32, 48>(ctx, c, items)) != hipSuccess) return e;
-    if (nmax > 48 && (e = go_gram<48, 64>(ctx, c, items)) != hipSuccess) return e;
-    if ((e = go_tridiag<0, 32>(ctx, c, items)) != hipSuccess) return e;
-    if (nmax > 32 && (e = go_tridiag<32, 48>(ctx, c, items)) != hipSuccess) return e;
-    if (nmax > 48 && (e = go_tridiag<48, 64>(ctx, c, items)) != hipSuccess) return e;
+    if ((e = go_gram<0, 32>(ctx, c, items, seg)) != hipSuccess) return e;
+    if (nmax > 32 && (e = go_gram<32, 48>(ctx, c, items, seg)) != hipSuccess) return e;
+    if (nmax > 48 && (e = go_gram<48, 64>(ctx, c, items, seg)) != hipSuccess) return e;
+    if ((e = go_tridiag<0, 32>(ctx, c, items, seg)) != hipSuccess) return e;
+    if (nmax > 32 && (e = go_tridiag<32, 48>(ctx, c, items, seg)) != hipSuccess) return e;
+    if (nmax > 48 && (e = go_tridiag<48, 64>(ctx, c, items, seg)) != hipSuccess) return e;
     {
         const size_t lds = (size_t)2 * kEigChaseLanes * nmax * sizeof(double);
         e = hipFuncSetAttribute((const void*)dort_eig_chase_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
@@ -100,9 +107,9 @@ hipError_t eig(smrt_dort_ctx* ctx, const DevBatch& c, long long items) {
         hipLaunchKernelGGL(dort_eig_chase_kernel, dim3((unsigned)((items + kEigChaseLanes - 1) / kEigChaseLanes)), dim3(kEigChaseLanes), lds, ctx->stream, c, ctx->stage, items);
         if ((e = hipGetLastError()) != hipSuccess) return e;
     }
-    if ((e = go_vectors<0, 32>(ctx, c, items)) != hipSuccess) return e;
-    if (nmax > 32 && (e = go_vectors<32, 48>(ctx, c, items)) != hipSuccess) return e;
-    if (nmax > 48 && (e = go_vectors<48, 64>(ctx, c, items)) != hipSuccess) return e;
+    if ((e = go_vectors<0, 32>(ctx, c, items, seg)) != hipSuccess) return e;
+    if (nmax > 32 && (e = go_vectors<32, 48>(ctx, c, items, seg)) != hipSuccess) return e;
+    if (nmax > 48 && (e = go_vectors<48, 64>(ctx, c, items, seg)) != hipSuccess) return e;
     return hipSuccess;
 }
 }  // namespace smrt_launch
